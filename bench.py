@@ -2,6 +2,7 @@
 """bench.py -- GCN-layer edges/s of the MI355X hot path (BASELINE.json metric), one JSON line.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + the last timed step's output as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -212,6 +213,24 @@ def build_c5(dev, rank, world, layout, multi, n_chunks=None):
                                                 long_row_threshold=thr)
     ublocks, iblocks = sh.rank_blocks(r, c, v, rank, make)
     return sh, None, ublocks, iblocks, r, c, v
+
+
+DUMP_SAMPLE_ROWS = 131072
+
+
+def dump_outputs(out_dir, E):
+    """--dump-outputs: the [N, 64] fp32 table the last timed step propagated, the array a caller of the propagation receives.
+    All of it is 384 MB at config 5, so DIR gets DUMP_SAMPLE_ROWS of its rows drawn by a fixed seed (exact fp32 values), their
+    ids, and the float64 sum of every row of the whole table (~45 MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = E.shape[0]
+    ids = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:min(DUMP_SAMPLE_ROWS, n)].sort().values
+    sample = E.index_select(0, ids.to(E.device)).cpu().numpy()
+    row_sums = E.sum(dim=1, dtype=torch.float64).cpu().numpy()
+    np.save(os.path.join(out_dir, "propagated_rows_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(out_dir, "propagated_rows_sample_ids.npy"), ids.numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "propagated_row_sums.npy"), row_sums.astype(np.float64))
+    log("dumped the last timed step's output to %s: %d of %d rows + every row's sum" % (out_dir, ids.numel(), n))
 
 
 def cpu_baseline(r, c, v, n, max_seconds=25.0):
@@ -977,7 +996,12 @@ def main():
     ap.add_argument("--chunks", type=int, default=None, help="row chunks per rank of the allgather layout (default: auto)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group / sharding-plan self-test: no device work, no numbers (runs without a GPU)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the propagated [N, 64] table) as "
+                         "DIR/<name>.npy: a fixed, seeded sample of its rows plus the float64 sum of every row (single GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.headline_only:
         args.no_extra = args.no_cpu_baseline = args.no_pmc = True
     if args.pmc_child:
@@ -998,6 +1022,8 @@ def main():
         raise SystemExit("--layout dslice needs 1, 2, 4 or 8 ranks (64 columns / ranks = a slice width the kernel has)")
     if args.dry_run:
         return dry_run(args, rank, world)
+    if args.dump_outputs and (world > 1 or args.force_dist):
+        raise SystemExit("--dump-outputs needs a single-GPU run (the propagated table is sharded across ranks otherwise)")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
     torch.cuda.set_device(local_rank)
@@ -1111,6 +1137,8 @@ def main():
         L.dt = timed_steps(step, args.steps)
         L.timed = False
         tele_end = tele.read()                        # right after the closing fence
+        if args.dump_outputs:                         # what the last timed step left, before anything else runs
+            dump_outputs(args.dump_outputs, bufs[(N_LAYERS - 1) % 2])
         own_s = local_t["own"]
         # ... and UNDER LOAD, outside the timed region: ~0.15 s of the same launches are enqueued (asynchronous), the sensors
         # are read while the GPU is still working through them -- the clocks the timed launches actually ran at

@@ -16,6 +16,14 @@ def observed(name, value, floor):
     return value
 
 
+def config_digest(value):
+    """a configuration value as a short digest (tests/golden/reference_api.json keeps the reference's values this way):
+    canonical JSON -- dict keys sorted, list order kept, int / float / bool / str told apart -- hashed"""
+    import hashlib
+    import json
+    return hashlib.sha256(json.dumps(value, sort_keys=True, default=repr).encode()).hexdigest()[:16]
+
+
 def write_dataset(root, golden):
     ds = os.path.join(str(root), "baby")
     os.makedirs(ds, exist_ok=True)

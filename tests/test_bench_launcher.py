@@ -57,3 +57,25 @@ def test_bench_single_gpu_dry_run_needs_no_launcher(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     line = _one_line(r.stdout)
     assert line["n_gpus"] == 1 and "launching" not in r.stderr
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files under 64 MB in all at the headline table's size (1.5M x 64), the sampled
+    rows are the table's own values at ids that do not depend on the table, and every row's float64 sum is there."""
+    import numpy as np
+    import torch
+    import bench
+    n = 1_500_000
+    E = torch.rand(n, 64, generator=torch.Generator().manual_seed(5)) - 0.5
+    bench.dump_outputs(str(tmp_path / "a"), E)
+    bench.dump_outputs(str(tmp_path / "b"), torch.zeros(n, 64))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["propagated_row_sums.npy", "propagated_rows_sample.npy", "propagated_rows_sample_ids.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 2 ** 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    ids = got["propagated_rows_sample_ids"]
+    assert np.array_equal(ids, np.load(tmp_path / "b" / "propagated_rows_sample_ids.npy"))
+    assert ids.shape == (bench.DUMP_SAMPLE_ROWS,) and np.all(np.diff(ids) > 0) and ids[-1] < n
+    np.testing.assert_array_equal(got["propagated_rows_sample"], E.numpy()[ids.astype(np.int64)])
+    np.testing.assert_allclose(got["propagated_row_sums"], E.double().sum(1).numpy(), rtol=0, atol=1e-12)

@@ -228,97 +228,101 @@ def test_config_helpers_for_added_keys():
     assert not lazy_adam_enabled(Cfg(base, device=gpu, hip_fused_adam=False, lazy_feature_adam=True), big)
 
 
-REF_SRC = "/root/reference/src"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference tree only exists in the build container")
+def _reference_api():
+    """what tests/golden/make_golden_reference_api.py recorded from the unmodified reference (values as digests)"""
+    import json
+    with open(os.path.join(GOLDEN, "reference_api.json")) as f:
+        return json.load(f)
+
+
+def _digest_diff(ref, mine):
+    """keys of `ref` (key -> digest) that `mine` (key -> value) lacks or holds with another value"""
+    from tests._env import config_digest
+    return sorted(k for k, d in ref.items() if k not in mine or config_digest(mine[k]) != d)
+
+
 def test_every_reference_model_has_a_plugin_and_an_equal_config():
     """Drop-in surface: each `src/models/<name>.py` of the reference has a same-named plugin exposing the same class,
     and each `configs/model/<Name>.yaml`, `configs/dataset/*.yaml` parses to the reference's values (ours may add keys
     to overall.yaml, never change one)."""
     import importlib
     import yaml
-    ref_models = sorted(f[:-3] for f in os.listdir(os.path.join(REF_SRC, "models")) if f.endswith(".py"))
+    api = _reference_api()
+    ref_models = api["models"]
+    assert len(ref_models) == 21
     ours = sorted(f[:-3] for f in os.listdir(os.path.join(ROOT, "mmrec_amd", "models")) if f.endswith(".py") and f[0] != "_")
     assert set(ref_models) <= set(ours), sorted(set(ref_models) - set(ours))
-    for sub in ("model", "dataset"):
-        ref_dir = os.path.join(REF_SRC, "configs", sub)
-        for f in sorted(os.listdir(ref_dir)):
-            mine = os.path.join(ROOT, "mmrec_amd", "configs", sub, f)
-            assert os.path.exists(mine), mine
-            with open(os.path.join(ref_dir, f)) as a, open(mine) as b:
-                assert yaml.safe_load(a) == yaml.safe_load(b), f
-            if sub == "model":
-                name = f[:-5]
-                mod = importlib.import_module("mmrec_amd.models." + name.lower())
-                assert hasattr(mod, name), name
-    with open(os.path.join(REF_SRC, "configs", "overall.yaml")) as a, open(os.path.join(ROOT, "mmrec_amd", "configs", "overall.yaml")) as b:
-        ref, mine = yaml.safe_load(a), yaml.safe_load(b)
-    assert {k: mine.get(k) for k in ref} == ref
+    files = [f for f in api["config_files"] if f != "overall.yaml"]
+    assert sum(f.startswith("model/") for f in files) == 21 and any(f.startswith("dataset/") for f in files)
+    for f in files:
+        mine = os.path.join(ROOT, "mmrec_amd", "configs", f)
+        assert os.path.exists(mine), mine
+        with open(mine) as b:
+            parsed = yaml.safe_load(b)
+        ref = api["config_files"][f]
+        assert sorted(parsed) == sorted(ref) and not _digest_diff(ref, parsed), (f, _digest_diff(ref, parsed))
+        if f.startswith("model/"):
+            name = f[len("model/"):-5]
+            mod = importlib.import_module("mmrec_amd.models." + name.lower())
+            assert hasattr(mod, name), name
+    with open(os.path.join(ROOT, "mmrec_amd", "configs", "overall.yaml")) as b:
+        mine = yaml.safe_load(b)
+    assert not _digest_diff(api["config_files"]["overall.yaml"], mine), _digest_diff(api["config_files"]["overall.yaml"], mine)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference tree only exists in the build container")
-def test_knn_graph_helpers_equal_the_reference_functions(monkeypatch):
+def test_knn_graph_helpers_equal_the_reference_functions():
     """utils.utils kNN-graph helpers (kept for model code written against the reference's API): same values as the
-    reference's functions on random inputs incl. rows that sum to 0, dense and sparse, every normalisation."""
-    import importlib.util
-    import sys
-    spec = importlib.util.spec_from_file_location("_ref_utils_utils", os.path.join(REF_SRC, "utils", "utils.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    shim = importlib.util.spec_from_file_location(
-        "torch_scatter", os.path.join(ROOT, "tests", "golden", "_shims", "torch_scatter", "__init__.py"))
-    mod = importlib.util.module_from_spec(shim)
-    shim.loader.exec_module(mod)
-    monkeypatch.setitem(sys.modules, "torch_scatter", mod)       # imported lazily inside the reference's sparse helper
+    reference's functions (tests/golden/reference_knn_helpers.npz: their seeded inputs and outputs) incl. rows that sum
+    to 0, dense and sparse, every normalisation.  The fixture equals ours bit for bit where it was written; on another
+    CPU a BLAS product or a row sum may round in another order, hence 1e-6 relative on computed values (selections and
+    indices stay exact)."""
     from mmrec_amd.utils import utils as ours
-    g = torch.Generator().manual_seed(3)
-    feats = torch.randn(40, 12, generator=g)
-    sim = ours.build_sim(feats)
-    assert torch.equal(sim, ref.build_sim(feats))
-    assert torch.equal(ours.build_knn_neighbourhood(sim, 5), ref.build_knn_neighbourhood(sim, 5))
-    adj = torch.relu(torch.randn(30, 30, generator=g))
-    adj[4] = 0.0                                                                  # an empty row: 0, not inf / nan
-    assert torch.equal(ours.compute_normalized_laplacian(adj), ref.compute_normalized_laplacian(adj))
+    g = {k: torch.from_numpy(v) for k, v in np.load(os.path.join(GOLDEN, "reference_knn_helpers.npz")).items()}
+
+    def same(a, b):
+        torch.testing.assert_close(a, b, rtol=1e-6, atol=0)
+    same(ours.build_sim(g["feats"]), g["sim"])
+    assert torch.equal(ours.build_knn_neighbourhood(g["sim"], 5), g["neighbourhood_5"])
+    adj = g["adj"]
+    assert float(adj[4].abs().sum()) == 0.0                                       # an empty row: 0, not inf / nan
+    same(ours.compute_normalized_laplacian(adj), g["normalized_laplacian"])
     for norm in ("sym", "rw", "none"):
-        assert torch.equal(ours.get_dense_laplacian(adj, norm), ref.get_dense_laplacian(adj, norm))
-        assert torch.equal(ours.build_knn_normalized_graph(adj, 4, False, norm), ref.build_knn_normalized_graph(adj, 4, False, norm))
-        a, b = ours.build_knn_normalized_graph(adj, 4, True, norm), ref.build_knn_normalized_graph(adj, 4, True, norm)
-        assert torch.equal(a._indices(), b._indices()) and torch.allclose(a._values(), b._values(), rtol=1e-6, atol=0)
-        ei = torch.randint(0, 30, (2, 200), generator=g)
-        w = torch.rand(200, generator=g)
-        (i1, w1), (i2, w2) = ours.get_sparse_laplacian(ei, w, 30, norm), ref.get_sparse_laplacian(ei, w.clone(), 30, norm)
-        assert torch.equal(i1, i2) and torch.allclose(w1, w2, rtol=1e-6, atol=0)
+        same(ours.get_dense_laplacian(adj, norm), g["dense_laplacian_" + norm])
+        same(ours.build_knn_normalized_graph(adj, 4, False, norm), g["knn_dense_" + norm])
+        a = ours.build_knn_normalized_graph(adj, 4, True, norm)
+        assert torch.equal(a._indices(), g["knn_sparse_indices_" + norm])
+        same(a._values(), g["knn_sparse_values_" + norm])
+        i1, w1 = ours.get_sparse_laplacian(g["edge_index_" + norm], g["edge_weight_" + norm], 30, norm)
+        assert torch.equal(i1, g["sparse_laplacian_indices_" + norm])
+        same(w1, g["sparse_laplacian_weights_" + norm])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference tree only exists in the build container")
-def test_config_objects_equal_the_reference_configs(tmp_path, monkeypatch):
+def test_config_objects_equal_the_reference_configs():
     """`Config(model, dataset, overrides, mg)`: for every model, with and without the Mirror-Gradient file, every key
     the reference's merged configuration holds has the same value here (hyper-parameter list order included); ours only
-    adds keys.  The reference resolves ./configs from the working directory: it is built inside a scratch directory
-    whose `configs` links to the reference's."""
-    import importlib.util
-    import sys
-    os.symlink(os.path.join(REF_SRC, "configs"), tmp_path / "configs")
-    monkeypatch.chdir(tmp_path)
-    spec = importlib.util.spec_from_file_location("_ref_configurator", os.path.join(REF_SRC, "utils", "configurator.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    adds keys.  The reference's side: tests/golden/reference_api.json (make_golden_reference_api.py)."""
     from mmrec_amd.utils.configurator import Config
-    models = sorted(f[:-5] for f in os.listdir(os.path.join(REF_SRC, "configs", "model")))
+    from tests._env import config_digest
+    api = _reference_api()
+    models = sorted({k.split("/")[0] for k in api["final_configs"]})
     assert len(models) == 21
     for name in models:
         for mg in (False, True):
+            ref = api["final_configs"]["%s/mg=%d" % (name, mg)]
             over = {"gpu_id": 0, "use_gpu": False, "learning_rate": 0.123, "brand_new_key": [1, 2]}
-            a, b = ref.Config(name, "sports", dict(over), mg), Config(name, "sports", dict(over), mg)
-            ra, rb = a.final_config_dict, b.final_config_dict
-            missing = [k for k in ra if k not in rb]
+            b = Config(name, "sports", dict(over), mg)
+            rb = dict(b.final_config_dict)
+            missing = [k for k in ref["values"] if k not in rb]
             assert not missing, (name, mg, missing)
-            diff = {k: (ra[k], rb[k]) for k in ra if ra[k] != rb[k] and k != "device"}
-            assert not diff, (name, mg, diff)
-            assert str(ra["device"]) == str(rb["device"])
-            assert a["no_such_key"] is None and b["no_such_key"] is None
+            device = rb.pop("device")
+            diff = [k for k in _digest_diff(ref["values"], rb) if k != "device"]
+            assert not diff, (name, mg, {k: rb[k] for k in diff})
+            assert config_digest(str(device)) == ref["values"]["device"]
+            assert ref["missing_key_is_none"] and b["no_such_key"] is None
 
 
 def test_ground_truth_csr_from_flat_lists_equals_per_list_sort():

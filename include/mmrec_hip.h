@@ -61,10 +61,10 @@ const char* mmrec_error_string(int err);
  * is reduced by one workgroup into `partials` (n_chunks x 64 fp32 workspace) and the chunks of a row
  * are then summed in order -- deterministic, no float atomics.  partials = n_chunks * d floats.
  * long_tickets (ABI 7; may be NULL): n_long int32 counters, ZERO before the first call and left at zero by every call.
- * With them, graphs of at most MMREC_SPMM_FUSED_REDUCE_MAX_ROWS rows finish a multi-chunk row inside the launch (the chunk
- * block that arrives last sums the partials, in the same order: same bits) instead of in a second launch -- these graphs
- * are cache resident and latency bound (Amazon-Baby: 18.5 -> 15.4 us per layer).  One graph's tickets / partials must not be
- * used by two launches at the same time.
+ * With them, a multi-chunk row is finished inside the launch (the chunk block that arrives last sums the partials, in the
+ * same order: same bits) instead of in a second launch, at every graph size (Amazon-Baby: 18.5 -> 15.4 us per layer; config 5:
+ * the 18-us second launch and its gap).  Without them (NULL) the second launch runs.  One graph's tickets / partials must not
+ * be used by two launches at the same time.
  *
  * Epilogue per row r (y = alpha * sum + beta * Z[r], Z may be NULL):
  *      Y[r] = y                         (Y may be NULL when only the running sum is wanted)
@@ -74,7 +74,6 @@ const char* mmrec_error_string(int err);
 #ifndef MMREC_SPMM_CHUNK
 #define MMREC_SPMM_CHUNK 512            /* nnz per long-row chunk (one workgroup) */
 #endif
-#define MMREC_SPMM_FUSED_REDUCE_MAX_ROWS (1 << 18)
 #define MMREC_SPMM_LONG_ROW_DEFAULT 32  /* long_row_threshold of HBM-sized graphs; cache-resident ones (<= 2^18 columns) run
                                           * 30 % faster with 16: mmrec_amd/hip_ops.py default_long_row_threshold */
 

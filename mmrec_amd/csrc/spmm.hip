@@ -11,9 +11,10 @@
 //
 // Load balance (power-law rows): rows longer than `long_t` are skipped by the row
 // blocks and cut into MMREC_SPMM_CHUNK-nonzero chunks, one workgroup each in the same launch (16
-// groups x 16-nonzero spans, LDS tree); partial rows go to a workspace and a second tiny launch
-// sums them in chunk order.  Short serial chains also keep small cache-resident graphs (Amazon-Baby)
-// from being bound by the latency of their longest row.  No float atomics:
+// groups x 16-nonzero spans, LDS tree); partial rows go to a workspace and are summed in chunk order
+// by the chunk block that arrives last (or, without tickets, by a second tiny launch).  Short serial
+// chains also keep small cache-resident graphs (Amazon-Baby) from being bound by the latency of their
+// longest row.  No float atomics:
 // the per-row summation order is fixed and independent of the row partition (multi-GPU == 1 GPU).
 #include "common.h"
 #include "spmm_narrow.h"
@@ -168,6 +169,8 @@ __device__ __forceinline__ void reduce_long_row(const float* __restrict__ partia
 
 // One launch covers both kinds of work: blocks [0, n_chunks) reduce one long-row chunk each (started
 // first: they are the longest dependency chains), blocks [n_chunks, ...) process 64 short rows each.
+// (Other block orders -- chunk blocks interleaved with row blocks, user rows mixed with item rows -- give the same bits and
+// lose at config 5: profiles/r07_spmm_block_order_rejected.patch, r07_spmm_phases.log.)
 template <int DCH, bool LG>
 __global__ __launch_bounds__(256) void spmm_rows_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
@@ -216,8 +219,8 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
                 }
             }
         }
-        // `tickets` (small, latency-bound graphs): the row is finished HERE by the chunk block that arrives last, instead of
-        // by a second launch (4.5 us of a 19 us Amazon-Baby layer for the 15 rows that span several chunks).  The partial
+        // `tickets`: the row is finished HERE by the chunk block that arrives last, instead of by a second launch (4.5 us
+        // of a 19 us Amazon-Baby layer for its 15 rows that span several chunks; the launch and its gap at config 5).  The partial
         // was written at agent scope; the wave that wrote it waits for the acknowledgement and takes a ticket; the block
         // holding the last ticket reads all partials at agent scope in the reduce kernel's order (same bits) and leaves
         // the ticket at zero for the next launch.
@@ -258,7 +261,7 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
     }
 }
 
-// One workgroup per long row that spans several chunks (the two-launch form: large graphs).
+// One workgroup per long row that spans several chunks (the two-launch form: a caller without tickets).
 template <int DCH, bool LG>
 __global__ __launch_bounds__(256) void spmm_long_reduce_kernel(
     const int32_t* __restrict__ long_rows, const int32_t* __restrict__ long_chunk_ptr, int n_long,
@@ -363,9 +366,8 @@ extern "C" int mmrec_spmm_csr_f32(const int32_t* rowptr, const int32_t* colidx, 
     // without a plan every row goes through the row kernel
     const int long_t = n_long > 0 ? long_row_threshold : INT32_MAX;
     const int nch = n_long > 0 ? n_chunks : 0;
-    // rows finished inside the launch (last-arriver) on the small, latency-bound graphs only: a large graph has
-    // thousands of multi-chunk rows and is bandwidth bound; its second launch costs nothing measurable
-    int32_t* tickets = (n_long > 0 && n_rows <= MMREC_SPMM_FUSED_REDUCE_MAX_ROWS) ? long_tickets : nullptr;
+    // with tickets, multi-chunk rows are finished inside the launch (last arriver) at every graph size; without, by a second launch
+    int32_t* tickets = n_long > 0 ? long_tickets : nullptr;
 #define MMREC_SPMM_CASE(D)                                                                               \
     case D:                                                                                              \
         launch_spmm<D>(s, blocks, nch, rowptr, colidx, vals, X, ep, n_rows, long_t, rows_per_group,      \
@@ -433,7 +435,7 @@ extern "C" int mmrec_spmm_csr_f32_layergcn(const int32_t* rowptr, const int32_t*
     const int blocks = (n_rows + 16 * rows_per_group - 1) / (16 * rows_per_group);
     const int long_t = n_long > 0 ? long_row_threshold : INT32_MAX;
     const int nch = n_long > 0 ? n_chunks : 0;
-    int32_t* tickets = (n_long > 0 && n_rows <= MMREC_SPMM_FUSED_REDUCE_MAX_ROWS) ? long_tickets : nullptr;
+    int32_t* tickets = n_long > 0 ? long_tickets : nullptr;
     launch_spmm<1, true>(s, blocks, nch, rowptr, colidx, vals, X, ep, n_rows, long_t, rows_per_group, long_rows,
                          long_chunk_ptr, n_long, partials, tickets);
     MMREC_RETURN_LAUNCH_STATUS();

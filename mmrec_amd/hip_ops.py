@@ -147,8 +147,8 @@ class CsrGraph:
             self.long_rows = torch.from_numpy(lr).to(dev)
             self.long_chunk_ptr = torch.from_numpy(cp).to(dev)
             self.max_row_chunks = int(np.diff(cp).max())          # chunks of the longest row (mmrec_spmm_rows_any_f32)
-            # last-arriver counters of the multi-chunk rows (small graphs finish such a row inside the launch): zero now,
-            # left at zero by every launch
+            # last-arriver counters of the multi-chunk rows (the launch finishes such a row itself): zero now, left at zero
+            # by every launch
             self.long_tickets = torch.zeros(self.n_long, dtype=torch.int32, device=dev)
         else:
             self.long_rows = self.long_chunk_ptr = self.long_tickets = None

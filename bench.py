@@ -3,8 +3,16 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + the last timed step's output as DIR/*.npy
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                 # + every companion measurement (minutes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: it builds the graph, runs the W warm-up and K timed steps, writes
+--dump-outputs if asked, and prints the line (value, ms_per_step, the roofline of the timed launches' HIP events, telemetry
+around the timed region).  --full adds everything that takes runs of its own: the CPU baselines, the Amazon-Baby and config-5
+companions under `extra` / `secondary`, the in-run rocprofv3 counter passes, the Trainer-level configurations, the config-5
+full-sort evaluation, the telemetry under load and, at N > 1, the exchange breakdown, replicas, weak scaling and the sharded
+training step.  The --no-* options leave parts of a --full run out.
 
 A "step" is one pass of the hot path over the whole graph: the 3-layer LightGCN-style user-item
 propagation E <- A E (d = 64, fp32) on the synthetic 10M-edge graph of BASELINE.json configs[4]
@@ -14,13 +22,13 @@ value = directed nnz x layers x steps / wall time (max over ranks), whole job.
 At N > 1 the rows are sharded (users and items blockwise, nnz-balanced) and the blocks are all-gathered over
 RCCL/xGMI after every layer, chunk by chunk under the next chunk's SpMM: the total work is fixed -> "scaling": "strong".
 
-roofline: HIP events on the launch stream bracket every SpMM call inside the timed region.  The headline
-`achieved` / `frac` are the COUNTER view: bytes the launch moves past L2 (rocprofv3 FETCH_SIZE, x2 on gfx950 for
-16-B/lane reads, + WRITE_SIZE; collected in-run by re-running a few launches of the same graph under rocprofv3, one
---pmc pass per counter set) / mean launch duration / 8 TB/s -- <= 1 by construction.  The gather-model figure of
-SURVEY.md 8d (264 B/nnz + 260 B/row: every nonzero fetches its X row; > 1 of peak because L2 absorbs hot rows), the
-compulsory bound (8 B/nnz + 516 B/row) and the L2 hit rate ride next to it.
-cpu_baseline (rank 0, N = 1): the reference's own operator, torch.sparse.mm on the uncoalesced COO
+roofline: HIP events on the launch stream bracket every SpMM call inside the timed region.  `achieved` / `frac` are the
+gather-model figure of SURVEY.md 8d (264 B/nnz + 260 B/row: every nonzero fetches its X row; > 1 of peak because L2
+absorbs hot rows); the compulsory bound (8 B/nnz + 516 B/row) rides next to it.  The COUNTER view (`traffic`,
+`frac_physical`, `l2_hit_rate`: bytes the launch moves past L2, rocprofv3 FETCH_SIZE x2 on gfx950 for 16-B/lane reads +
+WRITE_SIZE, / mean launch duration / 8 TB/s, <= 1 by construction) is collected in-run under --full by re-running a few
+launches of the same graph under rocprofv3, one --pmc pass per counter set; a plain run quotes the committed profile.
+cpu_baseline (--full, rank 0, N = 1): the reference's own operator, torch.sparse.mm on the uncoalesced COO
 adjacency (freedom.py:172), on a bounded sample (a few layers) with all host cores.
 """
 from __future__ import annotations
@@ -968,18 +976,25 @@ def dry_run(args, rank, world):
         dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not re-run launches under rocprofv3 for roofline.traffic")
-    ap.add_argument("--no-configs", action="store_true", help="skip extra.configs_step_ms (Trainer-level epochs of VBPR and the five "
-                                                              "north_star models at their BASELINE shapes, ~1 minute)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every companion measurement too: CPU baselines, Amazon-Baby and config-5 "
+                         "companions, in-run rocprofv3 counters, Trainer-level configurations, the config-5 full-sort "
+                         "evaluation, telemetry under load; at N > 1 the exchange breakdown, replicas, weak scaling and the "
+                         "sharded training step (minutes; a plain run only builds, warms up, times and prints)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the single-GPU companions under extra")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not re-run launches under rocprofv3 for "
+                                                          "roofline.traffic")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip extra.configs_step_ms (Trainer-level epochs of "
+                                                              "VBPR and the five north_star models at their BASELINE shapes, "
+                                                              "~1 minute)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="the timed region and nothing else (no companions, no CPU baseline, no counters): what "
+                    help="the timed region and nothing else, as a plain run (overrides --full): what "
                          "`rocprofv3 --kernel-trace --stats -- python bench.py --headline-only` profiles, so that the summary's "
                          "average SpMM duration is the timed launches' (profiles/r03_bench_headline_kernel_stats.csv)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
@@ -999,11 +1014,18 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (the propagated [N, 64] table) as "
                          "DIR/<name>.npy: a fixed, seeded sample of its rows plus the float64 sum of every row (single GPU)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.headline_only:
-        args.no_extra = args.no_cpu_baseline = args.no_pmc = True
+        args.full = False
+    if not args.full:         # a plain run: nothing that takes runs of its own
+        args.no_extra = args.no_cpu_baseline = args.no_pmc = args.no_configs = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.pmc_child:
         return pmc_child(args.pmc_child)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1140,16 +1162,17 @@ def main():
         if args.dump_outputs:                         # what the last timed step left, before anything else runs
             dump_outputs(args.dump_outputs, bufs[(N_LAYERS - 1) % 2])
         own_s = local_t["own"]
-        # ... and UNDER LOAD, outside the timed region: ~0.15 s of the same launches are enqueued (asynchronous), the sensors
-        # are read while the GPU is still working through them -- the clocks the timed launches actually ran at
-        for _ in range(max(1, min(200, int(0.15 / max(L.dt / args.steps, 1e-4))))):
-            step()
-        time.sleep(0.05)
-        tele_load = tele.read()
-        fence()
-        L.telemetry = {"start_of_timed_region": tele_start, "end_of_timed_region": tele_end, "under_load_after": tele_load,
-                       "source": "librocm_smi64 in-process (rsmi_dev_gpu_clk_freq_get SYS / MEM, socket power, junction "
-                                 "temperature), GPU index %d" % local_rank}
+        L.telemetry = {"start_of_timed_region": tele_start, "end_of_timed_region": tele_end}
+        if args.full:
+            # ... and UNDER LOAD, outside the timed region: ~0.15 s of the same launches are enqueued (asynchronous), the
+            # sensors are read while the GPU is still working through them -- the clocks the timed launches actually ran at
+            for _ in range(max(1, min(200, int(0.15 / max(L.dt / args.steps, 1e-4))))):
+                step()
+            time.sleep(0.05)
+            L.telemetry["under_load_after"] = tele.read()
+            fence()
+        L.telemetry["source"] = ("librocm_smi64 in-process (rsmi_dev_gpu_clk_freq_get SYS / MEM, socket power, junction "
+                                 "temperature), GPU index %d" % local_rank)
         L.timed_events = list(L.ev)
         L.per_rank = None
         L.exchange = None
@@ -1176,34 +1199,36 @@ def main():
             ex = {"nnz_per_rank": [int(x) for x in per_rank_nnz],
                   "nnz_imbalance_max_over_mean": float(per_rank_nnz.max() / per_rank_nnz.mean()),
                   "chunks_per_rank": sh.n_chunks}
-            b0 = L.prop.op.bytes_gathered
-            step()
-            fence()
-            inbound = L.prop.op.bytes_gathered - b0                     # payload bytes this rank received per step
-            compute_only = ShardedPropagator(sh, ublk, iblk, rank, local_spmm)
-            compute_only.op.exchange = False
-            t_comp = timed_steps(lambda: compute_only.propagate(X0, N_LAYERS, bufs=bufs), args.steps) / args.steps
+            if args.full:     # what the exchange costs on its own: runs of their own after the timed region
+                b0 = L.prop.op.bytes_gathered
+                step()
+                fence()
+                inbound = L.prop.op.bytes_gathered - b0                     # payload bytes this rank received per step
+                compute_only = ShardedPropagator(sh, ublk, iblk, rank, local_spmm)
+                compute_only.op.exchange = False
+                t_comp = timed_steps(lambda: compute_only.propagate(X0, N_LAYERS, bufs=bufs), args.steps) / args.steps
 
-            def comm_only():
-                for layer in range(N_LAYERS):
-                    works = []
-                    for _, lo, hi, rlo, rhi in L.prop.op.entries:
-                        works.append(dist.all_gather_into_tensor(bufs[layer % 2][rlo:rhi], bufs[layer % 2][lo:hi],
-                                                                 async_op=True))
-                    for w in works:
-                        w.wait()
-            comm_only()
-            t_comm = timed_steps(comm_only, args.steps) / args.steps
-            t_tot = L.dt / args.steps
-            ex.update({
-                "exchange_bytes_in_per_rank_per_step": int(inbound),
-                "ms_per_step_compute_only": t_comp * 1e3, "ms_per_step_exchange_only": t_comm * 1e3,
-                "ms_per_layer_compute_only": t_comp * 1e3 / N_LAYERS, "ms_per_layer_exchange_only": t_comm * 1e3 / N_LAYERS,
-                "xgmi_gbps_achieved": inbound / t_tot / 1e9,            # per GPU, inbound, inside the timed step
-                "xgmi_gbps_exchange_only": inbound / t_comm / 1e9,      # the same all-gathers with nothing else running
-                "overlap_frac": max(0.0, min(1.0, (t_comp + t_comm - t_tot) / max(min(t_comp, t_comm), 1e-9))),
-                "note_exchange": "per-GPU inbound payload of the per-layer all-gathers (fp32 rows); overlap_frac = share of "
-                                 "the shorter of {SpMMs, exchange} that ran hidden under the other"})
+                def comm_only():
+                    for layer in range(N_LAYERS):
+                        works = []
+                        for _, lo, hi, rlo, rhi in L.prop.op.entries:
+                            works.append(dist.all_gather_into_tensor(bufs[layer % 2][rlo:rhi], bufs[layer % 2][lo:hi],
+                                                                     async_op=True))
+                        for w in works:
+                            w.wait()
+                comm_only()
+                t_comm = timed_steps(comm_only, args.steps) / args.steps
+                t_tot = L.dt / args.steps
+                ex.update({
+                    "exchange_bytes_in_per_rank_per_step": int(inbound),
+                    "ms_per_step_compute_only": t_comp * 1e3, "ms_per_step_exchange_only": t_comm * 1e3,
+                    "ms_per_layer_compute_only": t_comp * 1e3 / N_LAYERS,
+                    "ms_per_layer_exchange_only": t_comm * 1e3 / N_LAYERS,
+                    "xgmi_gbps_achieved": inbound / t_tot / 1e9,            # per GPU, inbound, inside the timed step
+                    "xgmi_gbps_exchange_only": inbound / t_comm / 1e9,      # the same all-gathers with nothing else running
+                    "overlap_frac": max(0.0, min(1.0, (t_comp + t_comm - t_tot) / max(min(t_comp, t_comm), 1e-9))),
+                    "note_exchange": "per-GPU inbound payload of the per-layer all-gathers (fp32 rows); overlap_frac = share "
+                                     "of the shorter of {SpMMs, exchange} that ran hidden under the other"})
             L.exchange = ex
         if dslice:
             L.exchange = {"columns_per_rank": d_loc, "exchange_bytes_in_per_rank_per_step": 0,
@@ -1294,12 +1319,13 @@ def main():
         watchdog.start()
 
     # N > 1: what the exchange costs and how much of it hides under the SpMMs (allgather layout), the nnz balance
-    # of the cut, the no-exchange alternative (one full replica per GPU), a weak-scaling companion and a sharded
-    # training step -- all AFTER the timed region
+    # of the cut, and under --full the no-exchange alternative (one full replica per GPU), a weak-scaling companion and a
+    # sharded training step -- all AFTER the timed region
     dist_extra = None
     if multi:
         dist_extra = state["dist_extra"] = {}
         dist_extra.update(best.exchange or {})
+    if multi and args.full:
         if dslice:
             full = g
             xa = torch.rand(n_nodes, 64, device=dev, generator=torch.Generator(device=dev).manual_seed(0)) - 0.5
@@ -1334,62 +1360,61 @@ def main():
                               "GPUs: independent hyper-parameter runs); `value` is the sharded layout named in "
                               "config.parallelism")
 
-    # companion at every N: full-sort evaluation of all 1M users at config-5 size, users sharded over the ranks
+    # companion at every N (--full): full-sort evaluation of all 1M users at config-5 size, users sharded over the ranks
     c5_eval = None
-    try:
-        if args.headline_only:
-            raise RuntimeError("--headline-only")
-        ne = nnz_total // 2                       # sym_norm_coo: the first half are the user rows, sorted by (user, item)
-        eu_all, ei_all = r[:ne], c[:ne] - sh.n_users
-        E = bufs[(N_LAYERS - 1) % 2] if (not multi or args.layout in ("allgather", "dslice")) else None
-        if dslice and world > 1:
-            # the ONE exchange of the feature-sliced layout: the ranks' column slices of the final tables -> the full rows the
-            # ranking needs (an all-gather of [N, 64 / P] blocks, then columns interleaved back; once per evaluation)
-            fence()
-            t_x = time.perf_counter()
-            parts = torch.empty(world * n_nodes, d_loc, device=dev)                  # rank-major row blocks
-            dist.all_gather_into_tensor(parts, E)
-            E = parts.view(world, n_nodes, d_loc).permute(1, 0, 2).reshape(n_nodes, 64).contiguous()
-            del parts
-            fence()
-            dist_extra["eval_table_allgather_ms"] = (time.perf_counter() - t_x) * 1e3
-            dist_extra["eval_table_allgather_bytes_in_per_rank"] = int((world - 1) * n_nodes * d_loc * 4)
-        if E is None:
-            ge = torch.Generator(device=dev).manual_seed(1)
-            Ue = torch.rand(sh.n_users, 64, device=dev, generator=ge) - 0.5
-            Ie = torch.rand(sh.n_items, 64, device=dev, generator=ge) - 0.5
-        elif multi and not dslice:
-            Ue, Ie = (t.contiguous() for t in sh.unpad(E))
-        else:
-            Ue, Ie = E[:sh.n_users].contiguous(), E[sh.n_users:].contiguous()
-        t_eval, warm_eval = c5_full_eval(dev, rank, world, Ue, Ie, eu_all, ei_all, sh.n_users, fence)
-        if multi:
-            ts = [t_eval, warm_eval.get("seconds_same_tables", 0.0), warm_eval.get("seconds_lists_of_moved_tables", 0.0)]
-            tt = torch.tensor(ts, device=dev, dtype=torch.float64)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            t_eval = float(tt[0].item())
-            for j, key in ((1, "seconds_same_tables"), (2, "seconds_lists_of_moved_tables")):
-                if key in warm_eval:
-                    warm_eval[key] = float(tt[j].item())
-        for key in ("same_tables", "lists_of_moved_tables"):
-            if "seconds_" + key in warm_eval:
-                warm_eval["users_per_s_" + key] = sh.n_users / warm_eval["seconds_" + key]
-        flop = 2.0 * sh.n_users * sh.n_items * 64
-        c5_eval = {"users_per_s": sh.n_users / t_eval, "seconds": t_eval,
-                   "useful_tflops": flop / t_eval / 1e12,            # one exact score per (user, item) pair
-                   # what the filter EXECUTES on the matrix cores: pass 2 over every candidate + pass 1 over every second
-                   # 64-candidate stage (>= 131,072 candidates: topk_filter.hip filter_plan) = 1.5 x the useful products
-                   "executed_tflops_f16": 1.5 * flop / t_eval / 1e12,
-                   "frac_mfma_f16_executed": 1.5 * flop / t_eval / 1e12 / MFMA_F16_PEAK_TF,
-                   # the round-2 review's yardstick (two full passes' worth of products over the call), kept for comparison
-                   "frac_mfma_f16_two_passes": 2 * flop / t_eval / 1e12 / MFMA_F16_PEAK_TF,
-                   "warm": warm_eval,
+    if args.full:
+        try:
+            ne = nnz_total // 2                       # sym_norm_coo: the first half are the user rows, sorted by (user, item)
+            eu_all, ei_all = r[:ne], c[:ne] - sh.n_users
+            E = bufs[(N_LAYERS - 1) % 2] if (not multi or args.layout in ("allgather", "dslice")) else None
+            if dslice and world > 1:
+                # the ONE exchange of the feature-sliced layout: the ranks' column slices of the final tables -> the full rows the
+                # ranking needs (an all-gather of [N, 64 / P] blocks, then columns interleaved back; once per evaluation)
+                fence()
+                t_x = time.perf_counter()
+                parts = torch.empty(world * n_nodes, d_loc, device=dev)                  # rank-major row blocks
+                dist.all_gather_into_tensor(parts, E)
+                E = parts.view(world, n_nodes, d_loc).permute(1, 0, 2).reshape(n_nodes, 64).contiguous()
+                del parts
+                fence()
+                dist_extra["eval_table_allgather_ms"] = (time.perf_counter() - t_x) * 1e3
+                dist_extra["eval_table_allgather_bytes_in_per_rank"] = int((world - 1) * n_nodes * d_loc * 4)
+            if E is None:
+                ge = torch.Generator(device=dev).manual_seed(1)
+                Ue = torch.rand(sh.n_users, 64, device=dev, generator=ge) - 0.5
+                Ie = torch.rand(sh.n_items, 64, device=dev, generator=ge) - 0.5
+            elif multi and not dslice:
+                Ue, Ie = (t.contiguous() for t in sh.unpad(E))
+            else:
+                Ue, Ie = E[:sh.n_users].contiguous(), E[sh.n_users:].contiguous()
+            t_eval, warm_eval = c5_full_eval(dev, rank, world, Ue, Ie, eu_all, ei_all, sh.n_users, fence)
+            if multi:
+                ts = [t_eval, warm_eval.get("seconds_same_tables", 0.0), warm_eval.get("seconds_lists_of_moved_tables", 0.0)]
+                tt = torch.tensor(ts, device=dev, dtype=torch.float64)
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                t_eval = float(tt[0].item())
+                for j, key in ((1, "seconds_same_tables"), (2, "seconds_lists_of_moved_tables")):
+                    if key in warm_eval:
+                        warm_eval[key] = float(tt[j].item())
+            for key in ("same_tables", "lists_of_moved_tables"):
+                if "seconds_" + key in warm_eval:
+                    warm_eval["users_per_s_" + key] = sh.n_users / warm_eval["seconds_" + key]
+            flop = 2.0 * sh.n_users * sh.n_items * 64
+            c5_eval = {"users_per_s": sh.n_users / t_eval, "seconds": t_eval,
+                       "useful_tflops": flop / t_eval / 1e12,            # one exact score per (user, item) pair
+                       # what the filter EXECUTES on the matrix cores: pass 2 over every candidate + pass 1 over every second
+                       # 64-candidate stage (>= 131,072 candidates: topk_filter.hip filter_plan) = 1.5 x the useful products
+                       "executed_tflops_f16": 1.5 * flop / t_eval / 1e12,
+                       "frac_mfma_f16_executed": 1.5 * flop / t_eval / 1e12 / MFMA_F16_PEAK_TF,
+                       # the round-2 review's yardstick (two full passes' worth of products over the call), kept for comparison
+                       "frac_mfma_f16_two_passes": 2 * flop / t_eval / 1e12 / MFMA_F16_PEAK_TF,
+                       "warm": warm_eval,
 
-                   "what": "score + mask + top-50 of all %d users x %d items (the propagated embeddings of the timed step), "
-                           "users sharded x%d, item table replicated, no exchange" % (sh.n_users, sh.n_items, world)}
-        del Ue, Ie
-    except Exception as ex:
-        c5_eval = {"error": repr(ex)}
+                       "what": "score + mask + top-50 of all %d users x %d items (the propagated embeddings of the timed step), "
+                               "users sharded x%d, item table replicated, no exchange" % (sh.n_users, sh.n_items, world)}
+            del Ue, Ie
+        except Exception as ex:
+            c5_eval = {"error": repr(ex)}
     state["c5_eval"] = c5_eval
     if watchdog is not None:
         watchdog.cancel()
@@ -1584,7 +1609,8 @@ def emit_line(args, rank, world, multi, sh, g, r, c, v, dev, n_nodes, nnz_total,
             line["per_rank"] = state.get("per_rank")
             line["layouts"] = state.get("layouts")        # both layouts' edges/s, per-rank compute and per-layer exchange times
             line["roofline"]["per_rank_frac_gather_model"] = (state.get("per_rank") or {}).get("spmm_frac_gather_model")
-        line.setdefault("extra", {})["c5_full_eval"] = c5_eval
+        if c5_eval is not None:  # measured under --full
+            line.setdefault("extra", {})["c5_full_eval"] = c5_eval
         if isinstance(c5_eval, dict) and "users_per_s" in c5_eval:
             w = c5_eval.get("warm") or {}
             line["config"]["c5_full_eval_users_per_s"] = {"cold": c5_eval["users_per_s"], "warm_same_tables": w.get("users_per_s_same_tables"),

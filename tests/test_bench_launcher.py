@@ -1,7 +1,8 @@
 """CPU: `python bench.py --gpus N` with no torchrun environment starts N ranks itself and prints ONE JSON line
 (round-2 review, item 2: without this an 8-GPU node would yield eight N = 1 numbers), and the torchrun form of the
 driver contract keeps working.  `--dry-run` runs everything of an N-rank run except the device work: launcher, process
-group (gloo here), the nnz-balanced row cut, one collective, rank 0's line."""
+group (gloo here), the nnz-balanced row cut, one collective, rank 0's line.  A plain run measures the headline alone;
+`--full` adds the companions."""
 import json
 import os
 import socket
@@ -79,3 +80,33 @@ def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
     assert ids.shape == (bench.DUMP_SAMPLE_ROWS,) and np.all(np.diff(ids) > 0) and ids[-1] < n
     np.testing.assert_array_equal(got["propagated_rows_sample"], E.numpy()[ids.astype(np.int64)])
     np.testing.assert_allclose(got["propagated_row_sums"], E.double().sum(1).numpy(), rtol=0, atol=1e-12)
+
+
+def test_bench_plain_run_leaves_companions_to_full():
+    """a plain run measures the headline alone; --full turns every companion on, the --no-* options refine --full, and
+    --headline-only is a plain run whatever else is given"""
+    import bench
+    parts = ("no_extra", "no_cpu_baseline", "no_pmc", "no_configs")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and all(getattr(plain, p) for p in parts)
+    full = bench.parse_args(["--full"])
+    assert full.full and not any(getattr(full, p) for p in parts)
+    some = bench.parse_args(["--full", "--no-configs", "--no-pmc"])
+    assert some.full and some.no_configs and some.no_pmc and not some.no_extra and not some.no_cpu_baseline
+    hl = bench.parse_args(["--full", "--headline-only"])
+    assert not hl.full and all(getattr(hl, p) for p in parts)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_alone(tmp_path):
+    """the whole plain single-GPU run on the device: one line with the headline fields, no companion measured"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                       cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _one_line(r.stdout)
+    assert line["unit"] == "edges/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["roofline"]["launches_timed"] == 2 * 3
+    for key in ("cpu_baseline", "cpu_baseline_full_eval", "secondary", "extra"):
+        assert key not in line, key
+    assert "under_load_after" not in line["telemetry"]

@@ -9,7 +9,7 @@
 #   tests:<expr>           pytest tests -m gpu -k "<expr>"      (use + for spaces: tests:linear+and+guard)
 #   file:<path>[:<expr>]   pytest <path> -m gpu [-k expr] -s
 #   smoke                  __graft_entry__.smoke()
-#   bench[:<flags>]        python bench.py <flags>  -> bench.json          (flags with + for spaces: bench:--no-cpu-baseline)
+#   bench[:<flags>]        python bench.py --full <flags>  -> bench.json   (flags with + for spaces: bench:--no-cpu-baseline)
 #   headline_trace         rocprofv3 --kernel-trace --stats -- python bench.py --headline-only -> headline_kernel_stats.csv
 #   trace:<script+args>    rocprofv3 --kernel-trace --stats -- python <script args> -> <script>_kernel_stats.csv (top 30 printed)
 #   pmc:<workload>         python tools/pmc_kernels.py <workload> (topk | linear | spmm): counters in their own passes
@@ -44,7 +44,7 @@ for step in "$@"; do
     file)    f=${arg%%:*}; k=""; [[ "$arg" == *:* ]] && k=${arg#*:}
              (timeout $T python -m pytest $f -m gpu -q -s -p no:cacheprovider ${k:+-k "$k"} > $log 2>&1; echo rc=$? >> $log); tail -6 $log ;;
     smoke)   (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1; echo rc=$? >> $log); tail -2 $log ;;
-    bench)   (timeout $T python bench.py $arg > $out/bench${arg:+_$(echo $arg | tr -c 'A-Za-z0-9' '_' | cut -c1-30)}.json 2> $log; echo rc=$? >> $log); tail -2 $log | cut -c1-300
+    bench)   (timeout $T python bench.py --full $arg > $out/bench${arg:+_$(echo $arg | tr -c 'A-Za-z0-9' '_' | cut -c1-30)}.json 2> $log; echo rc=$? >> $log); tail -2 $log | cut -c1-300
              head -c 600 $out/bench*.json | head -c 600; echo ;;
     headline_trace)
              rm -rf $out/_trace

@@ -58,7 +58,7 @@ const char* mmrec_error_string(int err);
  * Rows longer than `long_row_threshold` are not handled by the row kernel; the caller lists them
  * in a plan (host-built, see mmrec_spmm_plan_*): long_rows[n_long] (row ids, ascending),
  * long_chunk_ptr[n_long+1] (prefix sum of ceil(deg / MMREC_SPMM_CHUNK) per long row).  Each chunk
- * is reduced by one workgroup into `partials` (n_chunks x 64 fp32 workspace) and the chunks of a row
+ * is reduced by one workgroup into `partials` (n_chunks x d fp32 workspace) and the chunks of a row
  * are then summed in order -- deterministic, no float atomics.  partials = n_chunks * d floats.
  * long_tickets (ABI 7; may be NULL): n_long int32 counters, ZERO before the first call and left at zero by every call.
  * With them, a multi-chunk row is finished inside the launch (the chunk block that arrives last sums the partials, in the
@@ -69,6 +69,7 @@ const char* mmrec_error_string(int err);
  * Epilogue per row r (y = alpha * sum + beta * Z[r], Z may be NULL):
  *      Y[r] = y                         (Y may be NULL when only the running sum is wanted)
  *      acc_out[r] = acc_scale * (acc_in[r] + y)      (when acc_out != NULL; acc_in may alias acc_out)
+ * Y and acc_out must not be X (other rows still gather from it): MMREC_ERR_BAD_ARG.
  * which is how the LightGCN layer mean (1/(L+1) * sum_l E_l) is accumulated without a stack+mean pass.
  * ---------------------------------------------------------------------------------------------- */
 #ifndef MMREC_SPMM_CHUNK
@@ -100,6 +101,8 @@ int mmrec_spmm_rows_f32(const int32_t* rowptr, const int32_t* colidx, const floa
 /* ABI 12: the same for ANY listed row of a d = 64 graph, rows spanning several chunks included (one workgroup per such listed
  * row sums its chunks in the full launch's order: its bits).  max_row_chunks: the largest number of 512-nonzero chunks a row of
  * the graph's long-row plan spans (1: identical to mmrec_spmm_rows_f32; up to 480 = 245,760 nonzeros; more: MMREC_ERR_UNSUPPORTED).
+ * A listed row that spans more chunks than max_row_chunks (a value smaller than the plan's) is not computed: its Y row is
+ * written as quiet NaN.
  * For a training step that reads the LAST user-item layer (freedom.py:169-177) at its batch rows only: popular items are in
  * every batch and their rows span dozens of chunks. */
 int mmrec_spmm_rows_any_f32(const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* X,
@@ -120,7 +123,7 @@ int mmrec_spmm_csr_f32_layergcn(const int32_t* rowptr, const int32_t* colidx, co
                                 int32_t n_chunks, float* partials, int32_t* long_tickets, mmrec_stream_t stream);
 /* Host-side plan helpers (pure CPU, rowptr is a HOST pointer).  count: returns n_long and n_chunks;
  * fill: writes long_rows[n_long] and long_chunk_ptr[n_long+1] (host arrays the caller copies to the
- * device).  partials workspace = n_chunks * 64 * 4 bytes. */
+ * device).  partials workspace = n_chunks * d * 4 bytes (d: the row width of the SpMM call). */
 int mmrec_spmm_plan_count(const int32_t* rowptr_host, int32_t n_rows, int32_t long_row_threshold,
                           int32_t* n_long, int32_t* n_chunks);
 int mmrec_spmm_plan_fill(const int32_t* rowptr_host, int32_t n_rows, int32_t long_row_threshold,

@@ -353,7 +353,7 @@ extern "C" int mmrec_spmm_csr_f32(const int32_t* rowptr, const int32_t* colidx, 
     if (acc_out && !acc_in) return MMREC_ERR_BAD_ARG;
     if (n_long > 0 && (!long_rows || !long_chunk_ptr || !partials || n_chunks <= 0))
         return MMREC_ERR_BAD_ARG;
-    if (Y == X) return MMREC_ERR_BAD_ARG;  // other rows still gather from X
+    if (Y == X || acc_out == X) return MMREC_ERR_BAD_ARG;  // other rows still gather from X
     if (narrow)
         return spmm_narrow_launch(rowptr, colidx, vals, X, Y, Z, acc_in, acc_out, n_rows, d, alpha, beta, acc_scale,
                                   n_long > 0 ? long_row_threshold : INT32_MAX, long_rows, long_chunk_ptr, n_long,

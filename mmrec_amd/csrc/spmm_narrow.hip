@@ -215,7 +215,11 @@ __global__ __launch_bounds__(256) void spmm_pull_long_rows_kernel(
     if (e - s <= long_t || e - s <= MMREC_SPMM_CHUNK) return;       // uniform
     const int t = threadIdx.x & 15, g = threadIdx.x >> 4;
     const int n_ch = (e - s + MMREC_SPMM_CHUNK - 1) / MMREC_SPMM_CHUNK;
-    if (n_ch > max_chunks) return;                                  // (the host sized max_chunks from the graph's plan)
+    if (n_ch > max_chunks) {        // more chunks than the caller's max_row_chunks: a loud row, not what Y held (no LDS touched)
+        const float qnan = __uint_as_float(0x7fc00000u);
+        if (g == 0) reinterpret_cast<float4*>(Y)[(size_t)i * 16 + t] = make_float4(qnan, qnan, qnan, qnan);
+        return;                                                     // uniform
+    }
     const float4* X4 = reinterpret_cast<const float4*>(X);
     for (int c = 0; c < n_ch; ++c) {
         const int cs = s + c * MMREC_SPMM_CHUNK, ce = min(cs + MMREC_SPMM_CHUNK, e);

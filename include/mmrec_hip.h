@@ -196,6 +196,8 @@ int mmrec_gather_scale_add_bwd_f32(const float* E, const int64_t* ids, int32_t b
  *   two terms may name the same E / dE: the item table's positive and negative rows).  A term whose S_t is 0 gets coef 0 in
  *   mode 1, as torch.norm's backward does.  ids[t] NULL: rows 0 .. batch[t] - 1 of E[t] (a whole table: bm3.py:146's
  *   EmbLoss(u, i)).  E, ids, batch, dE are HOST arrays of n_terms entries (copied into the launch).
+ *   Two terms' dE tables must be the SAME pointer or must not overlap (a whole table named by one term only is added without
+ *   atomics).
  * replaces: the per-term mmrec_gather_sqnorm_fwd_f32 / mmrec_gather_scale_add_bwd_f32 calls and the ~20 elementwise
  * launches between them (a quarter of a LayerGCN / VBPR step at Amazon-Baby size). */
 #define MMREC_ROWS_REG_MAX_TERMS 6

@@ -454,12 +454,18 @@ __global__ __launch_bounds__(256) void rows_reg_bwd_kernel(const RegTerms a, int
     const int b = blockIdx.x * 16 + (threadIdx.x >> 4);
     if (b >= a.batch[t]) return;
     const float c = g[0] * coef[t];
-    const bool store = a.ids[t] == nullptr && a.exclusive[t];      // a whole table named by this term only: every element once
+    // a whole table named by this term only: every element is met once, by one lane -- a plain read-add-store (no atomics),
+    // still `+=` as the header says: a caller's accumulated gradient stays
+    const bool alone = a.ids[t] == nullptr && a.exclusive[t];
     for (int k = lane16; k < d4; k += 16) {
         const size_t i = (size_t)(a.ids[t] ? a.ids[t][b] : b) * d4 + k;
         const float4 v = f4_scale(c, reinterpret_cast<const float4*>(a.E[t])[i]);
-        if (store) reinterpret_cast<float4*>(a.dE[t])[i] = v;
-        else atomic_add_f4(a.dE[t] + i * 4, v);
+        if (alone) {
+            float4* dst = reinterpret_cast<float4*>(a.dE[t]) + i;
+            *dst = f4_add(*dst, v);
+        } else {
+            atomic_add_f4(a.dE[t] + i * 4, v);
+        }
     }
 }
 

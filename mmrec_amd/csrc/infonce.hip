@@ -60,7 +60,8 @@ __global__ __launch_bounds__(256) void nce_prep_kernel(const float* __restrict__
     const float ia = 1.0f / fmaxf(na, 1e-12f), ic = 1.0f / fmaxf(nc, 1e-12f);
     reinterpret_cast<float4*>(v1)[(size_t)b * 16 + lane16] = f4_scale(ia, a);
     reinterpret_cast<float4*>(v2)[(size_t)b * 16 + lane16] = f4_scale(ic, c);
-    if (lane16 == 0) { inv1[b] = ia; inv2[b] = ic; }
+    // sign bit: the clamp was active -- the norm is then a constant of the backward, as in row_normalize_fwd_kernel
+    if (lane16 == 0) { inv1[b] = na > 1e-12f ? ia : -ia; inv2[b] = nc > 1e-12f ? ic : -ic; }
 }
 
 // MODE 0: own = rows i of view 1, other = columns j of view 2; output ttl_part[split][i]
@@ -203,7 +204,8 @@ __global__ __launch_bounds__(256) void nce_reduce_kernel(const float* __restrict
     if (threadIdx.x == 0) out[0] = scale * red[0];
 }
 
-// dE[id] += (dvn - vn <vn, dvn>) * inv_norm   with dvn = sum of the split partials (fixed order)
+// dE[id] += (dvn - vn <vn, dvn>) * inv_norm   with dvn = sum of the split partials (fixed order); a row below F.normalize's
+// clamp (0 < ||x|| <= 1e-12) was divided by the constant 1e-12: dE[id] += dvn * 1e12, as autograd of F.normalize gives
 __global__ __launch_bounds__(256) void nce_scatter_kernel(const float* __restrict__ vn,
                                                           const float* __restrict__ inv,
                                                           const float* __restrict__ dpart,
@@ -216,8 +218,9 @@ __global__ __launch_bounds__(256) void nce_scatter_kernel(const float* __restric
     float4 d = f4_zero();
     for (int s = 0; s < NCE_SPLIT; ++s)
         d = f4_add(d, reinterpret_cast<const float4*>(dpart + ((size_t)s * B + b) * 64)[lane16]);
-    const float proj = row16_sum(f4_dot(x, d));
-    const float iv = inv[b];
+    const float dot = row16_sum(f4_dot(x, d));
+    const float proj = inv[b] > 0.f ? dot : 0.f;       // clamp active (sign bit, nce_prep_kernel): x / 1e-12, nothing to project out
+    const float iv = fabsf(inv[b]);
     float* dst = dE + (size_t)ids[b] * 64 + lane16 * 4;
     unsafeAtomicAdd(dst + 0, (d.x - x.x * proj) * iv);
     unsafeAtomicAdd(dst + 1, (d.y - x.y * proj) * iv);

@@ -990,10 +990,10 @@ class _BprWeightedTotal(torch.autograd.Function):
 
 def bpr_weighted_total(U, users, terms, weights, variant=BPR_LOGSIG, reduction="mean", joint_grad=False):
     """sum_t weights[t] * bpr_loss(U, I_t, users, pos_t, neg_t) as ONE scalar (freedom.py:197-211: the id term + reg_weight times
-    the modality terms) -- two launches forward, one backward (ABI 14); `hip_deterministic` or more than MMREC_BPR_MAX_TERMS terms:
-    the per-term form."""
+    the modality terms) -- two launches forward, one backward (ABI 14); `hip_deterministic`, more than MMREC_BPR_MAX_TERMS terms
+    or tables that share memory without being the same table (`_one_buffer_per_table`): the per-term form."""
     terms = list(terms)
-    if DETERMINISTIC or not 1 <= len(terms) <= 4:
+    if DETERMINISTIC or not 1 <= len(terms) <= 4 or not _one_buffer_per_table([I for I, _, _ in terms]):
         losses = bpr_losses_shared_users(U, users, terms, variant, reduction, joint_grad=joint_grad)
         total = 0.0
         for w, l in zip(weights, losses):
@@ -1151,15 +1151,35 @@ class _RowsReg(torch.autograd.Function):
 ROWS_REG_SQUARED, ROWS_REG_NORM = 0, 1
 
 
+def _one_buffer_per_table(tables):
+    """True when the multi-term backward kernels may give every distinct data_ptr() ONE dense gradient buffer: any two
+    tables are either the same table (same pointer, same shape, same requires_grad) or do not share memory at all.  Views of one
+    another's storage -- T[:k] next to T, two overlapping row ranges, a detached alias of a live tensor -- are not: a buffer
+    sized by the first would be written past its end by the second, or a constant's gradient folded into the live tensor's."""
+    seen = []
+    for E in tables:
+        if not E.is_contiguous():                  # (the fused ops take .contiguous() copies of such operands: the byte range below
+            return False                           # would not be the view's)
+        lo = E.data_ptr()
+        span = (lo, lo + E.numel() * E.element_size(), tuple(E.shape), bool(E.requires_grad))
+        for other in seen:
+            if span[0] < other[1] and other[0] < span[1] and span != other:
+                return False
+        seen.append(span)
+    return True
+
+
 def rows_reg(terms, mode, scale=1.0):
     """The regulariser of a training step over batch rows, fused: scale * sum_t ||E_t[ids_t]||_F^2 (mode ROWS_REG_SQUARED: the L2
     regulariser of layergcn.py:154-161 / lattice.py:214-216) or scale * sum_t ||E_t[ids_t]||_F (ROWS_REG_NORM: EmbLoss,
     common/loss.py:46-51).  terms = [(table [n, 64 k], ids [B]) ...].  Two launches forward, one backward, whatever the number
-    of terms; `hip_deterministic`, more than MMREC_ROWS_REG_MAX_TERMS terms or tables that are views of one another's storage
-    take the per-term ops."""
+    of terms; `hip_deterministic`, more than MMREC_ROWS_REG_MAX_TERMS terms or tables that share memory without being the same
+    table (views of one another's storage, overlapping row ranges, a detached alias: `_one_buffer_per_table`) take the per-term
+    ops."""
     terms = list(terms)
     same_rows = len({E.shape[1] for E, _ in terms}) == 1
-    if DETERMINISTIC or len(terms) > 6 or not terms or not same_rows or any(not E.is_contiguous() for E, _ in terms):
+    if (DETERMINISTIC or len(terms) > 6 or not terms or not same_rows or any(not E.is_contiguous() for E, _ in terms)
+            or not _one_buffer_per_table([E for E, _ in terms])):
         total = 0.0
         for E, ids in terms:
             s = (E * E).sum() if ids is None else gather_sqnorm(E, ids)
@@ -1329,10 +1349,11 @@ class _CosineMeans(torch.autograd.Function):
 
 def cosine_means(terms):
     """sum_t w_t mean_b cosine_similarity(X_t[ix_t[b]], Y_t[iy_t[b]]) for terms = [(X, ix, Y, iy, w), ...] in one launch pair
-    (Y constant, indices may be None): BM3's six BYOL terms (bm3.py:129-144).  `hip_deterministic` or more than
-    MMREC_COSINE_MAX_TERMS terms: the per-term op."""
+    (Y constant, indices may be None): BM3's six BYOL terms (bm3.py:129-144).  `hip_deterministic`, more than
+    MMREC_COSINE_MAX_TERMS terms, or X operands that share memory without being the same table (`_one_buffer_per_table`): the
+    per-term op."""
     terms = list(terms)
-    if DETERMINISTIC or not terms or len(terms) > 8:
+    if DETERMINISTIC or not terms or len(terms) > 8 or not _one_buffer_per_table([X for X, *_ in terms]):
         total = 0.0
         for X, ix, Y, iy, w in terms:
             total = total + w * cosine_mean(X, ix, Y, iy)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MMREC_ABI_VERSION 14
+#define MMREC_ABI_VERSION 15
 #define MMREC_EMB_DIM 64 /* embedding_size the SpMM / BPR / top-K kernels are specialised for (overall.yaml:16) */
 
 #define MMREC_ERR_BAD_ARG 10001      /* null pointer / negative size / unsupported d or k */
@@ -317,6 +317,24 @@ int mmrec_linear_bwd_w_f32(const float* dY, const float* X, float* dW, float* db
                            int32_t F, int32_t out, void* workspace, mmrec_stream_t stream);
 int mmrec_linear_bwd_x_f32(const float* dY, const float* W, float* dX, int32_t n, int32_t F,
                            int32_t out, mmrec_stream_t stream);
+/* ABI 15 -- the projection of LISTED rows of a feature table, straight from the table (freedom.py:203-208, bm3.py:116 with
+ * lazy_projection: the batch's pos / neg rows): no [n, F] copy of the rows is written or read.
+ *   fwd  Y [n, 64] = T[ids] W^T + b                    split != 0: the split-operand kernel of mmrec_linear_fwd_split_f32 with its
+ *                                                      device-side domain guard and fp32 fix-up, 0: the fp32 LDS-DMA kernel
+ *   bwd  dW [64, F] = dY^T T[ids], db [64] = column sums of dY, dX [n, F] = dY W: COMPACT, one row per list position (the caller
+ *        adds the rows of duplicated ids into the table's gradient).  dW (with db or without) and dX may each be NULL.
+ * T [n_table, F] contiguous; ids [n] int64: values in [0, n_table) name a row, duplicates allowed, ANY other value (-1: "no
+ * row") reads as a row of zeros -- Y = b there, nothing added to dW -- and is never used as an address.  Row offsets are 64-bit:
+ * tables above 4 GiB are served.
+ * Served: out == 64 and F % 128 == 0 (MMREC_ERR_UNSUPPORTED otherwise).  The kernels, split plans and summation orders are those
+ * of the dense entry points for the same (n, F): every result equals, bit for bit, the dense call on a gathered copy of the rows.
+ * Deterministic (no float atomics), no host synchronisation, capture-safe.
+ * workspace: mmrec_linear_rows_workspace_bytes. */
+size_t mmrec_linear_rows_workspace_bytes(int32_t n, int32_t F, int32_t out);
+int mmrec_linear_rows_fwd_f32(const float* T, int64_t n_table, const int64_t* ids, const float* W, const float* b, float* Y,
+                              int32_t n, int32_t F, int32_t out, int32_t split, void* workspace, mmrec_stream_t stream);
+int mmrec_linear_rows_bwd_f32(const float* dY, const float* T, int64_t n_table, const int64_t* ids, const float* W, float* dW,
+                              float* db, float* dX, int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream);
 /* C[M, :N] = A[M, K] B[N, K]^T (+ bias[N], may be NULL); K % 32 == 0, N <= ldc <= 2 Mi (32-bit byte offsets within a 128-row block).
  * F.linear(x, W, b) is (A, B) = (x, W); its dX is (A, B) = (dY, W^T). */
 int mmrec_gemm_nt_f32(const float* A, const float* B, const float* bias, float* C, int32_t M, int32_t N,

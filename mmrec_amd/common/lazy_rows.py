@@ -66,6 +66,28 @@ class _GatherRows(torch.autograd.Function):
         return None, None, None
 
 
+class _ProjectRows(torch.autograd.Function):
+    """hip_ops.linear_rows on a row-lazy table: the rows' gradient is parked on the table as _GatherRows parks it"""
+
+    @staticmethod
+    def forward(ctx, weight, ids, W, b, table):
+        from mmrec_amd import hip_ops
+        ctx.table = table
+        ctx.has_b = b is not None
+        W = W.contiguous()
+        ctx.save_for_backward(weight, ids, W)
+        return hip_ops._linear_rows_fwd(weight.detach(), ids, W, None if b is None else b.contiguous())
+
+    @staticmethod
+    def backward(ctx, dY):
+        from mmrec_amd import hip_ops
+        weight, ids, W = ctx.saved_tensors
+        want_w = ctx.needs_input_grad[2] or (ctx.has_b and ctx.needs_input_grad[3])
+        dW, db, dX = hip_ops._linear_rows_bwd(dY, weight.detach(), ids, W, want_w, ctx.has_b, True)
+        ctx.table._pending.append((ids, dX))
+        return None, None, dW, db, None
+
+
 class LazyRowEmbedding(nn.Embedding):
     """nn.Embedding whose Adam update is applied per touched row (see module docstring).  Use `rows(ids)`."""
 
@@ -188,8 +210,8 @@ class LazyRowEmbedding(nn.Embedding):
             done.record(side)
         self._prefetched = (ids, done)
 
-    def rows(self, ids):
-        """up-to-date rows `ids` [len(ids), F], differentiable w.r.t. the table"""
+    def _up_to_date(self, ids):
+        """wait for a prefetched catch-up, or catch the listed rows up here; returns the contiguous id list"""
         ids = ids.contiguous()
         pf, self._prefetched = getattr(self, '_prefetched', None), None
         if pf is not None:
@@ -197,7 +219,19 @@ class LazyRowEmbedding(nn.Embedding):
         if pf is None or pf[0].data_ptr() != ids.data_ptr() or pf[0].numel() != ids.numel():
             with torch.no_grad():
                 self._catch_up(ids)
-        return _GatherRows.apply(self.weight, ids, self)
+        return ids
+
+    def rows(self, ids):
+        """up-to-date rows `ids` [len(ids), F], differentiable w.r.t. the table"""
+        return _GatherRows.apply(self.weight, self._up_to_date(ids), self)
+
+    def project_rows(self, ids, W, b=None):
+        """hip_ops.linear(self.rows(ids), W, b) without the [len(ids), F] copy of the rows (hip_ops.linear_rows: same bits);
+        ids of -1 on an `allow_missing` table read as zero rows.  Shapes the gathered kernels do not serve take the two steps."""
+        from mmrec_amd import hip_ops
+        if not hip_ops.linear_rows_served(self.weight, ids, W):
+            return hip_ops.linear(self.rows(ids), W, b)
+        return _ProjectRows.apply(self.weight, self._up_to_date(ids), W, b, self)
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         self.flush()                            # a checkpoint must hold dense Adam's values, not stale rows

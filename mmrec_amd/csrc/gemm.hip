@@ -35,6 +35,7 @@ constexpr int LIN_BM = 128, LIN_BK = 64, LIN_LD = LIN_BK + 4;  // LD/4 odd -> co
 constexpr int LIN_Q4 = LIN_BK / 4;          // float4 per staged row
 constexpr int LIN_RPP = 256 / LIN_Q4;       // rows staged per pass of the 256 threads
 constexpr int LIN_XP = LIN_BM / LIN_RPP, LIN_WP = 64 / LIN_RPP;
+constexpr int BW_BF_ZERO = 128;             // floats of g_zero_row: one 128-column segment of a dW tile row (the forward reads 32)
 
 // ---------------------------------------------------------------------------------------- forward
 // grid (ceil(n/128), ksplit); wave w owns rows w*32..+31 and all 64 outputs (2 accumulators).
@@ -110,6 +111,50 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
     }
 }
 
+// ------------------------------------------------------------------- gathered operand rows (ABI 15)
+// The `G` variants of the kernels below read row j of their X operand from T[ids[j]] instead of X[j] (mmrec_linear_rows_*: the
+// batch's feature rows projected straight out of the table, no [n, F] copy).  Only the ADDRESS of a lane's 16-byte piece changes:
+// a table of 500,000 x 4096 floats is 8 GB, past the 32-bit offset of a buffer descriptor, so the piece is fetched with
+// `global_load_lds_dwordx4` from a per-lane 64-bit address (the LDS side is the same wave-uniform base + lane x 16, the same one
+// count on vmcnt).  What the descriptors' bounds zero-filled -- the rows past n, the tiles issued past a chunk's end -- and every
+// id outside [0, n_table) read g_zero_row instead, 512 bytes of zeros in the code object (nothing to clear per call).  Tile walk, split plan, LDS image, swizzle and MFMA
+// sequence are untouched, so the results equal the dense kernels' on a gathered copy bit for bit.
+__device__ __attribute__((aligned(512))) const float g_zero_row[BW_BF_ZERO] = {};
+template <bool NT>
+__device__ __forceinline__ void lds_dma16_ptr(const void* src, unsigned lds) {
+    unsigned keep;
+    if (NT)
+        asm volatile(
+            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+            "global_load_lds_dwordx4 %2, off nt\n\ts_mov_b32 m0, %0"
+            : "=&s"(keep)
+            : "s"(lds), "v"(src)
+            : "memory");
+    else
+        asm volatile(
+            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+            "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+            : "=&s"(keep)
+            : "s"(lds), "v"(src)
+            : "memory");
+}
+// source of this lane's pieces of the forward tiles: row m0 + 32 wave + 8 j + lane / 8, 16-byte chunk swizzled as in the dense form;
+// kmask[j] = -1 for a row of the table (the tile's k offset is added to its source), 0 for the zero row (it is not)
+__device__ __forceinline__ void fwd_row_sources(const float* __restrict__ T, const int64_t* __restrict__ ids, int64_t n_table,
+                                                int m0, int n, int F, int wave, int lane, const char* (&px)[4], int (&kmask)[4]) {
+    int64_t idv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) idv[j] = ids[min(m0 + 32 * wave + 8 * j + (lane >> 3), n - 1)];      // (four loads in flight together)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int r = 32 * wave + 8 * j + (lane >> 3);
+        const bool ok = m0 + r < n && (unsigned long long)idv[j] < (unsigned long long)n_table;
+        const float* row = (ok ? T : g_zero_row) + (ok ? (size_t)idv[j] * F : (size_t)0);
+        kmask[j] = ok ? -1 : 0;
+        px[j] = reinterpret_cast<const char*>(row) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);
+    }
+}
+
 // ------------------------------------------------------------------- forward, LDS-DMA pipeline
 // Same tile (128 x 64 per workgroup, wave w owns rows 32w..+31) but the operands go HBM -> LDS with
 // `buffer_load_dwordx4 ... lds` (no staging VGPRs, no address VALU: scalar k offset + per-lane
@@ -120,12 +165,13 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
 // every 16-lane service group of ds_read_b128 ({0-3,12-15,20-27}, ...) cover all 64 banks.
 // Requires F % 32 == 0 (4096, 384, 4480 all are); other F take linear_fwd_kernel.
 constexpr int DM_BK = 32, DM_STAGES = 3;
-template <bool NT>
+template <bool NT, bool G = false>     // G: X is a table and row j of the operand is X[ids[j]] (see "gathered operand rows")
 __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __restrict__ X,
                                                                 const float* __restrict__ W,
                                                                 const float* __restrict__ bias,
                                                                 float* __restrict__ out, int n, int F,
-                                                                int k_chunk, const int* __restrict__ redo) {
+                                                                int k_chunk, const int* __restrict__ redo,
+                                                                const int64_t* __restrict__ ids = nullptr, int64_t n_table = 0) {
     __shared__ __attribute__((aligned(1024))) float Xs0[LIN_BM * DM_BK], Xs1[LIN_BM * DM_BK], Xs2[LIN_BM * DM_BK];
     __shared__ __attribute__((aligned(1024))) float Ws0[64 * DM_BK], Ws1[64 * DM_BK], Ws2[64 * DM_BK];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -138,10 +184,13 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __r
     const int T = (ke - kb) / DM_BK;
     const int rows_left = min(LIN_BM, n - m0);
     // probe bit 4: every workgroup streams the same 128 rows (L2 resident) instead of its own
-    const i32x4 rx = raw_rsrc(X + ((MMREC_GEMM_PROBE_MODE & 16) ? 0 : (size_t)m0 * F), (unsigned)rows_left * (unsigned)F * 4u);
+    const i32x4 rx = raw_rsrc(X + ((MMREC_GEMM_PROBE_MODE & 16) || G ? 0 : (size_t)m0 * F), G ? 0u : (unsigned)rows_left * (unsigned)F * 4u);
     const i32x4 rw = raw_rsrc(W, 64u * (unsigned)F * 4u);
     // per-lane source offsets of this wave's pieces (4 of X, 2 of W), swizzle on the source side
     int vx[4], vw[2];
+    const char* px[4];
+    int kmask[4];
+    if (G) fwd_row_sources(X, ids, n_table, m0, n, F, wave, lane, px, kmask);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int r = 32 * wave + 8 * j + (lane >> 3);
@@ -155,7 +204,10 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __r
     auto issue = [&](float* xs, float* ws, int t) {
         const int so = (kb + t * DM_BK) * 4;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) lds_dma16<NT>(rx, lds_addr(xs + (4 * wave + j) * 256), vx[j], so);
+        for (int j = 0; j < 4; ++j) {
+            if (G) lds_dma16_ptr<NT>(px[j] + (so & kmask[j]), lds_addr(xs + (4 * wave + j) * 256));
+            else lds_dma16<NT>(rx, lds_addr(xs + (4 * wave + j) * 256), vx[j], so);
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j)   // probe bit 5: W only for the first two tiles
             if (!(MMREC_GEMM_PROBE_MODE & 32) || t < 2) lds_dma16<false>(rw, lds_addr(ws + (2 * wave + j) * 256), vw[j], so);
@@ -274,13 +326,14 @@ __global__ __launch_bounds__(256) void linear_w_split_kernel(const float* __rest
     }
 }
 
-template <bool NT>
+template <bool NT, bool G = false>     // G: X is a table and row j of the operand is X[ids[j]] (see "gathered operand rows")
 __global__ __launch_bounds__(256, 2) void linear_fwd_dma_f16x3_kernel(const float* __restrict__ X,
                                                                       const float* __restrict__ Wsp,
                                                                       const float* __restrict__ bias,
                                                                       float* __restrict__ out, int n, int F,
                                                                       int k_chunk, float* __restrict__ rowmax_part,
-                                                                      int* __restrict__ redo) {
+                                                                      int* __restrict__ redo,
+                                                                      const int64_t* __restrict__ ids = nullptr, int64_t n_table = 0) {
     __shared__ __attribute__((aligned(1024))) float Xs0[LIN_BM * DM_BK], Xs1[LIN_BM * DM_BK], Xs2[LIN_BM * DM_BK];
     __shared__ __attribute__((aligned(1024))) float Ws0[64 * DM_BK], Ws1[64 * DM_BK], Ws2[64 * DM_BK];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -289,9 +342,12 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_f16x3_kernel(const floa
     const int kb = blockIdx.y * k_chunk, ke = min(kb + k_chunk, F);
     const int T = (ke - kb) / DM_BK;
     const int rows_left = min(LIN_BM, n - m0);
-    const i32x4 rx = raw_rsrc(X + (size_t)m0 * F, (unsigned)rows_left * (unsigned)F * 4u);
+    const i32x4 rx = raw_rsrc(X + (G ? 0 : (size_t)m0 * F), G ? 0u : (unsigned)rows_left * (unsigned)F * 4u);
     const i32x4 rw = raw_rsrc(Wsp, 64u * (unsigned)F * 4u);
     int vx[4], vw[2];
+    const char* px[4];
+    int kmask[4];
+    if (G) fwd_row_sources(X, ids, n_table, m0, n, F, wave, lane, px, kmask);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int r = 32 * wave + 8 * j + (lane >> 3);
@@ -318,7 +374,10 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_f16x3_kernel(const floa
         if (tt >= T) tt -= T;
         const int so = (kb + tt * DM_BK) * 4;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) lds_dma16<NT>(rx, lds_addr(xs + (4 * wave + j) * 256), vx[j], so);
+        for (int j = 0; j < 4; ++j) {
+            if (G) lds_dma16_ptr<NT>(px[j] + (so & kmask[j]), lds_addr(xs + (4 * wave + j) * 256));
+            else lds_dma16<NT>(rx, lds_addr(xs + (4 * wave + j) * 256), vx[j], so);
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j) lds_dma16<false>(rw, lds_addr(ws + (2 * wave + j) * 256), vw[j], so);
     };
@@ -994,10 +1053,12 @@ __global__ __launch_bounds__(256) void bwd_w_finish_kernel(const float* __restri
     reinterpret_cast<float4*>(dW)[i4] = f4_add(f4_add(t0, t1), f4_add(t2, t3));
 }
 
-template <bool NT>
+template <bool NT, bool G = false>     // G: X is a table and item j of the contraction is X[ids[j]] (see "gathered operand rows")
 __global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_kernel(const g_bf8* __restrict__ Asp_g,
                                                                                     const float* __restrict__ X,
-                                                                                    float* __restrict__ part, int n, int F, int n_chunk) {
+                                                                                    float* __restrict__ part, int n, int F, int n_chunk,
+                                                                                    const int64_t* __restrict__ ids = nullptr,
+                                                                                    int64_t n_table = 0) {
     constexpr int S = 3, AS = MMREC_BWD_W2_AS;
     __shared__ __attribute__((aligned(1024))) float Xr[S][BW_BK * BW_BF];      // X tiles [item][f], 3-stage ring (48 KB)
     __shared__ __attribute__((aligned(1024))) g_bf8 Ar[AS][12 * 64];           // split dY fragments of a tile (12 KB each)
@@ -1008,21 +1069,52 @@ __global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_ker
     const int nb = blockIdx.y * n_chunk, ne = min(nb + n_chunk, n);
     const int rows = ne - nb;
     const int T = (rows + BW_BK - 1) / BW_BK;
-    const i32x4 rx = raw_rsrc(X + (size_t)nb * F + f0, (unsigned)rows * (unsigned)F * 4u - (unsigned)f0 * 4u);
+    const i32x4 rx = raw_rsrc(X + (G ? 0 : (size_t)nb * F + f0), G ? 0u : (unsigned)rows * (unsigned)F * 4u - (unsigned)f0 * 4u);
     const i32x4 ra = raw_rsrc(reinterpret_cast<const char*>(Asp_g) + (size_t)(nb / BW_BK) * BW2_ATILE, (unsigned)T * (unsigned)BW2_ATILE);
     int vx[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) vx[j] = (2 * (2 * wave + j) + (lane >> 5)) * F * 4 + (lane & 31) * 16;
     const int va = lane * 16;
+    // G: the wave's two pieces of tile t are items 4 wave .. + 3 of the tile, two per piece.  Their ids are wave-uniform: read
+    // through the scalar cache (constant address space: no entry on vmcnt, which the ring below counts by hand) two tiles before
+    // their copies are issued, turned into addresses one tile before.  Items past the chunk, tiles past its end and ids outside
+    // the table take the zero row.
+    typedef const __attribute__((address_space(4))) int64_t* ids_sptr;
+    const char* nx[2];      // sources of the next tile to be issued
+    int64_t idn[4];         // ids of the tile after it
+    auto load_ids = [&](int t) {
+        const int item0 = nb + t * BW_BK + 4 * wave;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) idn[q] = ((ids_sptr)(unsigned long long)ids)[min(item0 + q, n - 1)];
+    };
+    auto sources = [&](int t) {      // from idn = the ids of tile t
+        const char* s[4];
+        const int item0 = nb + t * BW_BK + 4 * wave;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool ok = t < T && item0 + q < ne && (unsigned long long)idn[q] < (unsigned long long)n_table;
+            const long long off = ok ? (long long)idn[q] * F + f0 : 0;
+            s[q] = reinterpret_cast<const char*>((ok ? X : g_zero_row) + off);
+        }
+        nx[0] = ((lane >> 5) ? s[1] : s[0]) + (lane & 31) * 16;
+        nx[1] = ((lane >> 5) ? s[3] : s[2]) + (lane & 31) * 16;
+    };
     // a tile's fragments are 12 linear 1-KB pieces: wave w brings piece w, waves 0-3 also piece 8 + w
     auto issue_a = [&](int t) {
         const unsigned dst = lds_addr(reinterpret_cast<const float*>(&Ar[t % AS][0]));
         lds_dma16<false>(ra, dst + wave * 1024, va, t * BW2_ATILE + wave * 1024);
         if (wave < 4) lds_dma16<false>(ra, dst + (8 + wave) * 1024, va, t * BW2_ATILE + (8 + wave) * 1024);
     };
-    auto issue_x = [&](int t) {
+    auto issue_x = [&](int t) {      // G: tile t's sources are in nx; tile t + 1's are fetched behind the copies
 #pragma unroll
-        for (int j = 0; j < 2; ++j) lds_dma16<NT>(rx, lds_addr(&Xr[t % S][(2 * wave + j) * 256]), vx[j], t * BW_BK * F * 4);
+        for (int j = 0; j < 2; ++j) {
+            if (G) lds_dma16_ptr<NT>(nx[j], lds_addr(&Xr[t % S][(2 * wave + j) * 256]));
+            else lds_dma16<NT>(rx, lds_addr(&Xr[t % S][(2 * wave + j) * 256]), vx[j], t * BW_BK * F * 4);
+        }
+        if (G) {
+            sources(t + 1);
+            load_ids(t + 2);
+        }
     };
     const int i = lane & 31, h = lane >> 5;
     f32x16 acc0 = {0}, acc1 = {0};
@@ -1054,6 +1146,11 @@ __global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_ker
     // (AS = 3: A(0) A(1) X(0) X(1) | A(2) X(2) | ...: the newest 2 + nA copies may be in flight.)  Tiles past the end are issued
     // too: out of the descriptors' range, they fill with zeros and are never multiplied.
     if (T > 0) {
+        if (G) {
+            load_ids(0);
+            sources(0);
+            load_ids(1);
+        }
         issue_a(0);
         if (AS == 3) issue_a(1);
         issue_x(0);
@@ -1271,9 +1368,25 @@ extern "C" size_t mmrec_linear_workspace_bytes(int32_t n, int32_t F, int32_t out
     return fwd > bww ? fwd : bww;
 }
 
+namespace {
+// a gathered X operand: rows T[ids[j]] of a table with n_table rows (ids == nullptr: X itself, consecutive rows)
+struct RowList {
+    const int64_t* ids;
+    int64_t n_table;
+};
+int linear_fwd_f32_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
+                        void* workspace, mmrec_stream_t stream);
+}  // namespace
+
 extern "C" int mmrec_linear_fwd_f32(const float* X, const float* W, const float* b, float* Y,
                                     int32_t n, int32_t F, int32_t out, void* workspace,
                                     mmrec_stream_t stream) {
+    return linear_fwd_f32_impl(X, RowList{nullptr, 0}, W, b, Y, n, F, out, workspace, stream);
+}
+
+namespace {
+int linear_fwd_f32_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
+                        void* workspace, mmrec_stream_t stream) {
     if (out != 64 || F <= 0 || (F & 3)) return MMREC_ERR_UNSUPPORTED;
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
@@ -1290,7 +1403,14 @@ extern "C" int mmrec_linear_fwd_f32(const float* X, const float* W, const float*
     const dim3 grid(ceil_div(n, LIN_BM), nsplit);
     // X larger than the 256 MB Infinity Cache is read once per call: stream it non-temporal
     const bool nt = (size_t)n * F * sizeof(float) > ((size_t)192 << 20);
-    if (dma && nt)
+    if (g.ids) {      // (mmrec_linear_rows_fwd_f32 has checked F % 128 == 0: always the LDS-DMA kernel)
+        if (nt)
+            hipLaunchKernelGGL((linear_fwd_dma_kernel<true, true>), grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr,
+                               g.ids, g.n_table);
+        else
+            hipLaunchKernelGGL((linear_fwd_dma_kernel<false, true>), grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr,
+                               g.ids, g.n_table);
+    } else if (dma && nt)
         hipLaunchKernelGGL(linear_fwd_dma_kernel<true>, grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr);
     else if (dma)
         hipLaunchKernelGGL(linear_fwd_dma_kernel<false>, grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr);
@@ -1305,15 +1425,25 @@ extern "C" int mmrec_linear_fwd_f32(const float* X, const float* W, const float*
     }
     MMREC_RETURN_LAUNCH_STATUS();
 }
+}  // namespace
 
 // mmrec_linear_fwd_f32 on the 16-bit matrix cores with split operands (fp32-accurate: see linear_fwd_dma_f16x3_kernel).  F % 32 != 0
 // takes the fp32 kernels.  Rows / weights outside the split's domain (|.| >= 65520, inf, NaN, or a whole row below 2^-10) are
 // detected on the device and recomputed by the fp32 kernel in the same call (no host synchronisation): see the kernel's comment.
 // Workspace: mmrec_linear_workspace_bytes (slabs | split W | per-slab row maxima | redo flags).
+namespace {
+int linear_fwd_split_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
+                          void* workspace, mmrec_stream_t stream);
+}  // namespace
 extern "C" int mmrec_linear_fwd_split_f32(const float* X, const float* W, const float* b, float* Y, int32_t n, int32_t F,
                                           int32_t out, void* workspace, mmrec_stream_t stream) {
+    return linear_fwd_split_impl(X, RowList{nullptr, 0}, W, b, Y, n, F, out, workspace, stream);
+}
+namespace {
+int linear_fwd_split_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
+                          void* workspace, mmrec_stream_t stream) {
     if (out != 64 || F <= 0 || (F & 3)) return MMREC_ERR_UNSUPPORTED;
-    if ((F % DM_BK) != 0) return mmrec_linear_fwd_f32(X, W, b, Y, n, F, out, workspace, stream);
+    if ((F % DM_BK) != 0) return linear_fwd_f32_impl(X, g, W, b, Y, n, F, out, workspace, stream);
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     if (!X || !W || !Y || !workspace) return MMREC_ERR_BAD_ARG;
@@ -1332,8 +1462,16 @@ extern "C" int mmrec_linear_fwd_split_f32(const float* X, const float* W, const 
     hipLaunchKernelGGL(linear_w_split_kernel, dim3(64), dim3(256), 0, s, W, F, Wsp, redo, nblocks);
     float* dst = nsplit == 1 ? Y : part;
     const dim3 grid(nblocks, nsplit);
+    // (gathered: the same rule on the size of the rows that are READ, so that a row's k walk -- the NT form rotates it -- is the
+    // dense kernel's on the gathered copy)
     const bool nt = (size_t)n * F * sizeof(float) > ((size_t)192 << 20);
-    if (nt)
+    if (g.ids && nt)
+        hipLaunchKernelGGL((linear_fwd_dma_f16x3_kernel<true, true>), grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo,
+                           g.ids, g.n_table);
+    else if (g.ids)
+        hipLaunchKernelGGL((linear_fwd_dma_f16x3_kernel<false, true>), grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo,
+                           g.ids, g.n_table);
+    else if (nt)
         hipLaunchKernelGGL(linear_fwd_dma_f16x3_kernel<true>, grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo);
     else
         hipLaunchKernelGGL(linear_fwd_dma_f16x3_kernel<false>, grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo);
@@ -1343,12 +1481,19 @@ extern "C" int mmrec_linear_fwd_split_f32(const float* X, const float* W, const 
                            b, Y, (const float*)rowmax_part, redo);
     }
     // fix-up: the fp32 kernel over the flagged 128-row blocks (the others return at once), whole K per workgroup
-    if (nt)
+    if (g.ids && nt)
+        hipLaunchKernelGGL((linear_fwd_dma_kernel<true, true>), dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo,
+                           g.ids, g.n_table);
+    else if (g.ids)
+        hipLaunchKernelGGL((linear_fwd_dma_kernel<false, true>), dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo,
+                           g.ids, g.n_table);
+    else if (nt)
         hipLaunchKernelGGL(linear_fwd_dma_kernel<true>, dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo);
     else
         hipLaunchKernelGGL(linear_fwd_dma_kernel<false>, dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo);
     MMREC_RETURN_LAUNCH_STATUS();
 }
+}  // namespace
 
 // ---- ABI 11: the projection's backward on the 16-bit matrix cores (see the kernels' comment block) ----------------------------
 // Workspace layout (mmrec_linear_bwd_split_workspace_bytes): [W^T split: F x 256 B][wcs_inv: F + 256 floats][db partials:
@@ -1403,8 +1548,18 @@ extern "C" size_t mmrec_linear_bwd_split_workspace_bytes(int32_t n, int32_t F, i
 // out == 64 and F % 128 == 0 run the split-operand kernels; other shapes are handed to mmrec_linear_bwd_w_f32 /
 // mmrec_linear_bwd_x_f32 (same workspace).  Results: fp32-accurate (dW: error <= 2^-22 of sum |a b| per output + fp32
 // accumulation, any magnitudes; dX: 2^-21 with the operands scaled into fp16's range by exact powers of two).
+namespace {
+int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const float* W, float* dW, float* db, float* dX,
+                          int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream);
+}  // namespace
 extern "C" int mmrec_linear_bwd_split_f32(const float* dY, const float* X, const float* W, float* dW, float* db, float* dX,
                                           int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream) {
+    return linear_bwd_split_impl(dY, X, RowList{nullptr, 0}, W, dW, db, dX, n, F, out, workspace, stream);
+}
+namespace {
+// (g.ids: only from mmrec_linear_rows_bwd_f32, which has checked that the split kernels serve the shape)
+int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const float* W, float* dW, float* db, float* dX,
+                          int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream) {
     if (n < 0 || F <= 0 || out <= 0) return MMREC_ERR_BAD_ARG;
     if (!bwd_split_serves(n, F, out)) {
         if (dW) {
@@ -1445,7 +1600,13 @@ extern "C" int mmrec_linear_bwd_split_f32(const float* dY, const float* X, const
             hipLaunchKernelGGL(bwd_dy_split_kernel, dim3(w.dy_wgs), dim3(256), 0, s, dY, n, Asp_g, dbpart);
         }
         n_dbpart = w.dy_wgs;
-        if (big && (MMREC_BWD_NT & 1))
+        if (g.ids && big && (MMREC_BWD_NT & 1))
+            hipLaunchKernelGGL((linear_bwd_w_v2_kernel<true, true>), dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F,
+                               w.chunk, g.ids, g.n_table);
+        else if (g.ids)
+            hipLaunchKernelGGL((linear_bwd_w_v2_kernel<false, true>), dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F,
+                               w.chunk, g.ids, g.n_table);
+        else if (big && (MMREC_BWD_NT & 1))
             hipLaunchKernelGGL(linear_bwd_w_v2_kernel<true>, dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F, w.chunk);
         else
             hipLaunchKernelGGL(linear_bwd_w_v2_kernel<false>, dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F, w.chunk);
@@ -1474,6 +1635,50 @@ extern "C" int mmrec_linear_bwd_split_f32(const float* dY, const float* X, const
                                (const float*)wcs_inv, dX, n, F, ftiles);
     }
     MMREC_RETURN_LAUNCH_STATUS();
+}
+inline bool rows_serves(int F, int out) { return out == 64 && F > 0 && (F % BW_BF) == 0; }
+}  // namespace
+
+// ---- ABI 15: the projection of LISTED rows of a table, Y[j] = T[ids[j]] W^T + b, without the [n, F] copy of the rows --------
+// The same kernels, split plans and launches as mmrec_linear_fwd_f32 / mmrec_linear_fwd_split_f32 / mmrec_linear_bwd_split_f32
+// run on a gathered copy of the rows (bit-identical results); only the address of a row differs (see "gathered operand rows").
+// Workspace: what the dense entry points need for (n, F).
+extern "C" size_t mmrec_linear_rows_workspace_bytes(int32_t n, int32_t F, int32_t out) {
+    if (n <= 0 || !rows_serves(F, out)) return 0;
+    return mmrec_linear_bwd_split_workspace_bytes(n, F, out);
+}
+
+extern "C" int mmrec_linear_rows_fwd_f32(const float* T, int64_t n_table, const int64_t* ids, const float* W, const float* b,
+                                         float* Y, int32_t n, int32_t F, int32_t out, int32_t split, void* workspace,
+                                         mmrec_stream_t stream) {
+    if (!rows_serves(F, out)) return MMREC_ERR_UNSUPPORTED;
+    if (n < 0 || n_table < 0) return MMREC_ERR_BAD_ARG;
+    if (n == 0) return 0;
+    if (!T || !ids || !W || !Y || !workspace) return MMREC_ERR_BAD_ARG;
+    const RowList g{ids, n_table};
+    return split ? linear_fwd_split_impl(T, g, W, b, Y, n, F, out, workspace, stream)
+                 : linear_fwd_f32_impl(T, g, W, b, Y, n, F, out, workspace, stream);
+}
+
+extern "C" int mmrec_linear_rows_bwd_f32(const float* dY, const float* T, int64_t n_table, const int64_t* ids, const float* W,
+                                         float* dW, float* db, float* dX, int32_t n, int32_t F, int32_t out, void* workspace,
+                                         mmrec_stream_t stream) {
+    if (!rows_serves(F, out)) return MMREC_ERR_UNSUPPORTED;
+#if !MMREC_BWD_W_V2 || defined(MMREC_BWD_W_FP32)      // (probe builds with another dW kernel: no gathered form)
+    return MMREC_ERR_UNSUPPORTED;
+#endif
+    if (n < 0 || n_table < 0) return MMREC_ERR_BAD_ARG;
+    if ((dW && (!T || !ids)) || (dX && !W) || (db && !dW)) return MMREC_ERR_BAD_ARG;
+    if (n == 0) {       // an empty list: dW = 0, db = 0, nothing to write into dX
+        if (!dW) return 0;
+        hipStream_t s = mmrec_stream(stream);
+        if (dW) (void)hipMemsetAsync(dW, 0, (size_t)64 * F * sizeof(float), s);
+        if (db) (void)hipMemsetAsync(db, 0, 64 * sizeof(float), s);
+        MMREC_RETURN_LAUNCH_STATUS();
+    }
+    if (!dY || !workspace) return MMREC_ERR_BAD_ARG;
+    const RowList g{dW ? ids : nullptr, n_table};
+    return linear_bwd_split_impl(dY, T, g, W, dW, db, dX, n, F, out, workspace, stream);
 }
 
 // out = 64 j: the 64-column blocks of dY are handled one after the other (same workspace), each by

@@ -1478,6 +1478,84 @@ def linear(X, W, b=None):
     return _LinearWide.apply(X, W, b)
 
 
+def linear_rows_served(table, ids, W):
+    """True where `linear_rows` runs the gathered kernels (mmrec_linear_rows_*): device fp32 operands, W [64, F] with
+    F % 128 == 0, a contiguous table, int64 ids, and the split-operand projection (`LINEAR_F16X3`) on."""
+    return (LINEAR_F16X3 and isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and
+            table.dim() == 2 and table.is_contiguous() and W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and
+            W.shape[0] == 64 and W.shape[1] == table.shape[1] and table.shape[1] % 128 == 0 and
+            isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 1)
+
+
+def _linear_rows_fwd(table, ids, W, b):
+    lib = _lib.load()
+    n, F = ids.numel(), table.shape[1]
+    Y = torch.empty(n, 64, dtype=torch.float32, device=table.device)
+    ws = _ws(lib.mmrec_linear_rows_workspace_bytes(n, F, 64), table.device)
+    split = 1 if F >= LINEAR_SPLIT_MIN_F else 0         # _Linear.forward's choice
+    _lib.check(lib.mmrec_linear_rows_fwd_f32(_p(table), table.shape[0], _p(ids), _p(W), _p(b), _p(Y), n, F, 64, split, _p(ws),
+                                             _stream()), "linear_rows_fwd")
+    return Y
+
+
+def _linear_rows_bwd(dY, table, ids, W, want_w, has_b, want_x):
+    """dW, db, compact dX [len(ids), F] (each None where not wanted) of the gathered projection"""
+    lib = _lib.load()
+    n, F = ids.numel(), table.shape[1]
+    dY = dY.contiguous()
+    dW = db = dX = None
+    if want_w:
+        dW = torch.empty_like(W)
+        db = torch.empty(64, dtype=torch.float32, device=W.device) if has_b else None
+    if want_x:
+        dX = torch.empty(n, F, dtype=torch.float32, device=W.device)
+    if want_w or want_x:
+        ws = _ws(lib.mmrec_linear_rows_workspace_bytes(n, F, 64), W.device)
+        _lib.check(lib.mmrec_linear_rows_bwd_f32(_p(dY), _p(table), table.shape[0], _p(ids), _p(W), _p(dW), _p(db), _p(dX), n, F,
+                                                 64, _p(ws), _stream()), "linear_rows_bwd")
+    return dW, db, dX
+
+
+class _LinearRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, ids, W, b):
+        W = _chk(W.contiguous(), torch.float32, "W", 2)
+        if b is not None:
+            b = _chk(b.contiguous(), torch.float32, "b", 1)
+        ids = ids.contiguous()
+        ctx.save_for_backward(table, ids, W)
+        ctx.has_b = b is not None
+        return _linear_rows_fwd(table, ids, W, b)
+
+    @staticmethod
+    def backward(ctx, dY):
+        table, ids, W = ctx.saved_tensors
+        want_w = ctx.needs_input_grad[2] or (ctx.has_b and ctx.needs_input_grad[3])
+        dW, db, dX = _linear_rows_bwd(dY, table, ids, W, want_w, ctx.has_b, ctx.needs_input_grad[0])
+        dT = None
+        if dX is not None:
+            # the table's dense gradient exactly as autograd builds it for `table[ids]`: zeros + index_put_(accumulate)
+            dT = torch.zeros_like(table).index_put_((ids,), dX, accumulate=True)
+        return dT, None, dW, db
+
+
+def linear_rows(table, ids, W, b=None):
+    """linear(table[ids], W, b) -- the projection of the listed rows of a feature table (freedom.py:205-209, bm3.py:102-104
+    under `lazy_projection`) -- WITHOUT the [len(ids), F] copy of the rows: the kernels of `linear` read row ids[j] of the
+    table where they read row j of X (mmrec_linear_rows_*, ABI 15).  Y, dW, db and the rows of dX equal `linear` on
+    `table.index_select(0, ids)` bit for bit; the table's gradient is built from the compact dX by the call autograd makes for
+    `table[ids]` (a zero-filled buffer + index_put_(accumulate=True)).
+    Served by the kernels (`linear_rows_served`): device fp32 tensors, W [64, F], F % 128 == 0, a contiguous table, int64 ids,
+    `LINEAR_F16X3` on.  There an id outside [0, n_rows) -- -1 = "no row" -- reads as a row of zeros (Y = b, nothing in dW)
+    and is never used as an address; such ids are only meaningful while the table itself wants no gradient.
+    EVERY OTHER CASE (CPU tensors, other widths, a non-contiguous table, the split projection switched off) is the composition
+    `linear(table.index_select(0, ids), W, b)` through this module's `linear`: a fallback to the two-step form, not a CPU path
+    of the kernel."""
+    if linear_rows_served(table, ids, W):
+        return _LinearRows.apply(table, ids, W, b)
+    return linear(table.index_select(0, ids), W, b)       # (module-level name, looked up now: test stand-ins patch it)
+
+
 # ------------------------------------------------------------------------------------------------
 # P5 / P6  fused score + mask + top-K
 # ------------------------------------------------------------------------------------------------

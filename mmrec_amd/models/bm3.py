@@ -42,6 +42,7 @@ class BM3(RelabelledIdsMixin, AdjacentTablesMixin, FusedEvalMixin, GeneralRecomm
         n_feat = max([0] + [int(f.numel()) for f in (self.v_feat, self.t_feat) if f is not None])
         self.lazy_feature_adam = lazy_adam_enabled(config, n_feat) and self.lazy_projection
         self.lazy_prefetch = config['lazy_prefetch'] is not False    # new key: catch-up on a side stream (default on)
+        self.gathered_projection = config['hip_gathered_projection'] is not False   # new key: project the rows straight from the table
         table = LazyRowEmbedding if self.lazy_feature_adam else nn.Embedding
         self.norm_adj = norm_adj_graph(dataset.inter_matrix(form='coo').astype(np.float32),
                                        self.n_users, self.n_items, self.device)
@@ -112,15 +113,22 @@ class BM3(RelabelledIdsMixin, AdjacentTablesMixin, FusedEvalMixin, GeneralRecomm
         u_ori, i_ori = u_ori.contiguous(), i_ori.contiguous()
         users, items = interactions[0], interactions[1]
         lazy = self.lazy_projection
-        if lazy:
-            rows = (lambda emb: emb.rows(items)) if self.lazy_feature_adam else (lambda emb: emb.weight[items])
+        if lazy and getattr(self, 'gathered_projection', False):    # the kernels read the rows where they lie: no [B, F] copy (same bits)
+            if self.lazy_feature_adam:
+                project = lambda emb, trs: emb.project_rows(items, trs.weight, trs.bias)
+            else:
+                project = lambda emb, trs: hip_ops.linear_rows(emb.weight, items, trs.weight, trs.bias)
         else:
-            rows = lambda emb: emb.weight
+            if lazy:
+                rows = (lambda emb: emb.rows(items)) if self.lazy_feature_adam else (lambda emb: emb.weight[items])
+            else:
+                rows = lambda emb: emb.weight
+            project = lambda emb, trs: hip_ops.linear(rows(emb), trs.weight, trs.bias)
         t_on = v_on = None      # lazy: [B, 64] rows of the batch's items; else [n_items, 64]
         if self.t_feat is not None:
-            t_on = hip_ops.linear(rows(self.text_embedding), self.text_trs.weight, self.text_trs.bias)
+            t_on = project(self.text_embedding, self.text_trs)
         if self.v_feat is not None:
-            v_on = hip_ops.linear(rows(self.image_embedding), self.image_trs.weight, self.image_trs.bias)
+            v_on = project(self.image_embedding, self.image_trs)
         # dropout targets in the reference's order and shapes (u, i, t, v); lazy: the per-item masks of t and v
         ones = torch.ones_like(i_ori) if lazy else None
         # (lazy: the masks of t and v are drawn over `ones` per item in dataset order and gathered with the dataset's ids)

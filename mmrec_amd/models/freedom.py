@@ -87,6 +87,7 @@ class FREEDOM(RelabelledIdsMixin, AdjacentTablesMixin, FusedEvalMixin, GeneralRe
         n_feat = max([0] + [int(f.numel()) for f in (self.v_feat, self.t_feat) if f is not None])
         self.lazy_feature_adam = lazy_adam_enabled(config, n_feat) and self.lazy_projection
         self.lazy_prefetch = config['lazy_prefetch'] is not False    # new key: catch-up on a side stream (default on)
+        self.gathered_projection = config['hip_gathered_projection'] is not False   # new key: project the rows straight from the table
         self.pull_batch_rows = _batch_rows_wanted(config, self.n_users + self.n_items)   # new key `hip_pull_batch_rows`
         self.n_nodes = self.n_users + self.n_items
 
@@ -200,12 +201,19 @@ class FREEDOM(RelabelledIdsMixin, AdjacentTablesMixin, FusedEvalMixin, GeneralRe
         b = first_pos.shape[0]
         lp = torch.arange(b, device=rows.device)
         ln = lp + b
-        gather = (lambda emb: emb.rows(rows)) if self.lazy_feature_adam else (lambda emb: emb.weight[rows])
+        if getattr(self, 'gathered_projection', False):     # the kernels read the rows where they lie: no [2B, F] copy (same bits)
+            if self.lazy_feature_adam:
+                project = lambda emb, trs: emb.project_rows(rows, trs.weight, trs.bias)
+            else:
+                project = lambda emb, trs: hip_ops.linear_rows(emb.weight, rows, trs.weight, trs.bias)
+        else:
+            gather = (lambda emb: emb.rows(rows)) if self.lazy_feature_adam else (lambda emb: emb.weight[rows])
+            project = lambda emb, trs: hip_ops.linear(gather(emb), trs.weight, trs.bias)
         terms = [(first_table, first_pos, first_neg)]
         if self.t_feat is not None:
-            terms.append((hip_ops.linear(gather(self.text_embedding), self.text_trs.weight, self.text_trs.bias), lp, ln))
+            terms.append((project(self.text_embedding, self.text_trs), lp, ln))
         if self.v_feat is not None:
-            terms.append((hip_ops.linear(gather(self.image_embedding), self.image_trs.weight, self.image_trs.bias), lp, ln))
+            terms.append((project(self.image_embedding, self.image_trs), lp, ln))
         return terms
 
     def _loss_at_batch_rows(self, users, pos_items, neg_items, rows):

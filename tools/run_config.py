@@ -109,6 +109,8 @@ def main():
     ap.add_argument("--no-batch-rows", action="store_true", help="FREEDOM: hip_pull_batch_rows False (launches over all rows)")
     ap.add_argument("--fp32-linear", action="store_true", help="hip_linear_split False: projection forward + backward on the fp32-MFMA kernels")
     ap.add_argument("--lazy-adam", action="store_true", help="force the row-lazy exact Adam on the feature tables (automatic from 64 Mi elements)")
+    ap.add_argument("--two-step-projection", action="store_true", help="hip_gathered_projection False: FREEDOM / BM3 gather the batch's "
+                                                                        "feature rows, then project the copy (A/B of hip_ops.linear_rows)")
     ap.add_argument("--fast-forward", action="store_true", help="lazy_adam_fast_forward: closed-form catch-up (opt-in, not bit-identical)")
     args = ap.parse_args()
     cd = dict(device_neg_sampling=args.device_neg_sampling)
@@ -128,6 +130,8 @@ def main():
         cd['hip_pull_batch_rows'] = False
     if args.fp32_linear:
         cd['hip_linear_split'] = False
+    if args.two_step_projection:
+        cd['hip_gathered_projection'] = False
     if args.json:
         names = TIER if args.config == "tier" else [args.config]
         out = {n: run(n, cd, args.epochs) for n in names}

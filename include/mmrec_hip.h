@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MMREC_ABI_VERSION 15
+#define MMREC_ABI_VERSION 16
 #define MMREC_EMB_DIM 64 /* embedding_size the SpMM / BPR / top-K kernels are specialised for (overall.yaml:16) */
 
 #define MMREC_ERR_BAD_ARG 10001      /* null pointer / negative size / unsupported d or k */
@@ -339,6 +339,30 @@ int mmrec_linear_rows_bwd_f32(const float* dY, const float* T, int64_t n_table, 
  * F.linear(x, W, b) is (A, B) = (x, W); its dX is (A, B) = (dY, W^T). */
 int mmrec_gemm_nt_f32(const float* A, const float* B, const float* bias, float* C, int32_t M, int32_t N,
                       int32_t K, int32_t ldc, mmrec_stream_t stream);
+
+/* ABI 16 -- per-edge dot products (SDDMM): out[e] = <A[rows[e]], B[cols[e]]>, e < n_edges.
+ * replaces: build_sim restricted to the kept pairs -- lattice.py:141,146 (utils/utils.py:134-137, :119-122); GRCN's edge scores
+ *           torch.mul(x_i, x_j).sum(dim=-1) -- grcn.py:63; and d vals of the product with learned values, the backward of
+ *           torch.mm(self.item_adj, h) -- lattice.py:163 -- with respect to the adjacency's entries.
+ * A [n_a, d], B [n_b, d] row-major (B may be A); rows / cols [n_edges] int64 in any order, duplicates allowed; row offsets are
+ * 64-bit.  d = 8 / 16 / 32 or a multiple of 64 up to 384 -- what mmrec_spmm_csr_f32 accepts -- anything else:
+ * MMREC_ERR_UNSUPPORTED (checked before the pointers).  Null pointers or negative sizes: MMREC_ERR_BAD_ARG; n_edges == 0: 0 and
+ * no launch; n_edges > 2^31 - 1: MMREC_ERR_UNSUPPORTED.
+ * An edge whose row id is outside [0, n_a) or whose column id is outside [0, n_b) (-1: "no edge") gets out[e] = 0 and adds
+ * nothing in the backward; its id is never used as an address.
+ * Forward: one group of min(d, 64) / 4 lanes per edge, one float4 of each row per lane and 64 columns, one fma chain per lane
+ * (d / 16 terms; 4 for the slices), then a fixed butterfly over the group: the same bits run after run.
+ * Backward: dA[rows[e]] += g[e] * B[cols[e]] ; dB[cols[e]] += g[e] * A[rows[e]]  (either may be NULL; dA == dB allowed when
+ * A == B: both sums land in the one buffer).  fp32 atomics into caller-zeroed / accumulating buffers, so the order of a row's
+ * sum -- its last ulp -- can differ from run to run (callers that need fixed bits run the two sums as mmrec_spmm_csr_f32 over
+ * the edge list's CSR forms: hip_ops.edge_dot with a DynGraph).
+ * No synchronisation, no allocation, capture-safe, no global state. */
+int mmrec_edge_dot_f32(const float* A, int64_t n_a, const float* B, int64_t n_b,
+                       const int64_t* rows, const int64_t* cols, int64_t n_edges, int32_t d,
+                       float* out, mmrec_stream_t stream);
+int mmrec_edge_dot_bwd_f32(const float* g, const float* A, int64_t n_a, const float* B, int64_t n_b,
+                           const int64_t* rows, const int64_t* cols, int64_t n_edges, int32_t d,
+                           float* dA, float* dB, mmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,

@@ -1775,7 +1775,7 @@ class _SpMMVals(torch.autograd.Function):
     def forward(ctx, X, vals, dyn):
         X = X.contiguous()
         dyn.fwd.vals = vals.detach()[dyn.perm].contiguous()
-        Y = torch.empty(dyn.n_rows, EMB_DIM, dtype=torch.float32, device=X.device)
+        Y = torch.empty(dyn.n_rows, X.shape[1], dtype=torch.float32, device=X.device)
         spmm_raw(dyn.fwd, X, Y=Y)
         ctx.dyn = dyn
         ctx.save_for_backward(X, vals)
@@ -1789,16 +1789,115 @@ class _SpMMVals(torch.autograd.Function):
         dX = dvals = None
         if ctx.needs_input_grad[0]:
             dyn.bwd.vals = vals.detach()[dyn.perm_t].contiguous()
-            dX = torch.empty(dyn.n_cols, EMB_DIM, dtype=torch.float32, device=dY.device)
+            dX = torch.empty(dyn.n_cols, X.shape[1], dtype=torch.float32, device=dY.device)
             spmm_raw(dyn.bwd, dY, Y=dX)
-        if ctx.needs_input_grad[1]:
-            dvals = (dY[dyn.rows] * X[dyn.cols]).sum(-1)   # d val_e = <dY[row_e], X[col_e]>
+        if ctx.needs_input_grad[1]:                        # d val_e = <dY[row_e], X[col_e]>
+            if edge_dot_served(dY, X, dyn.rows, dyn.cols):
+                dvals = _edge_dot_fwd(dY, X, dyn.rows, dyn.cols)
+            else:
+                dvals = (dY[dyn.rows] * X[dyn.cols]).sum(-1)
         return dX, dvals, None
 
 
 def spmm_vals(dyn: DynGraph, X, vals):
-    """A(vals) @ X, differentiable in X and in the per-entry values (COO order of `dyn`)."""
+    """A(vals) @ X, differentiable in X and in the per-entry values (COO order of `dyn`), at every width `spmm_raw` serves.
+    The values' gradient is one dot product per entry: the SDDMM kernel (`EDGE_DOT`), no [n_edges, d] copies."""
     return _SpMMVals.apply(X, vals, dyn)
+
+
+# ------------------------------------------------------------------------------------------------
+# Per-edge dot products (SDDMM): the other half of the learned-values pattern (mmrec_edge_dot_*, ABI 16)
+# ------------------------------------------------------------------------------------------------
+EDGE_DOT = True       # False: every edge_dot call (and d vals of spmm_vals) is the gather-multiply-reduce composition (A/B runs)
+
+
+def _edge_width_served(d):
+    return d in SLICE_WIDTHS or (d > 0 and d % EMB_DIM == 0 and d <= 6 * EMB_DIM)
+
+
+def edge_dot_served(A, B, rows, cols):
+    """True where `edge_dot` runs the kernels (mmrec_edge_dot_*): device fp32 contiguous 2-D A, B of one served width (8 /
+    16 / 32 or 64 k <= 384: spmm_raw's), int64 1-D device rows / cols of equal length, and the `EDGE_DOT` switch on."""
+    def table(t):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
+                t.is_contiguous())
+
+    def ids(t):
+        return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
+    return bool(EDGE_DOT and table(A) and table(B) and A.shape[1] == B.shape[1] and _edge_width_served(A.shape[1]) and
+                ids(rows) and ids(cols) and rows.numel() == cols.numel())
+
+
+def _edge_dot_fwd(A, B, rows, cols):
+    lib = _lib.load()
+    out = torch.empty(rows.numel(), dtype=torch.float32, device=A.device)
+    _lib.check(lib.mmrec_edge_dot_f32(_p(A), A.shape[0], _p(B), B.shape[0], _p(rows), _p(cols), rows.numel(), A.shape[1],
+                                      _p(out), _stream()), "edge_dot")
+    return out
+
+
+class _EdgeDot(torch.autograd.Function):
+    """forward(A, B or None for `A is B`, rows, cols, dyn)"""
+
+    @staticmethod
+    def forward(ctx, A, B, rows, cols, dyn):
+        ctx.same = B is None
+        if ctx.same:
+            B = A
+        ctx.dyn, ctx.deterministic = dyn, DETERMINISTIC
+        ctx.save_for_backward(A, B, rows, cols)
+        return _edge_dot_fwd(A, B, rows, cols)
+
+    @staticmethod
+    def backward(ctx, g):
+        A, B, rows, cols = ctx.saved_tensors
+        dyn, same = ctx.dyn, ctx.same
+        want_a, want_b = ctx.needs_input_grad[0], (ctx.needs_input_grad[0] if same else ctx.needs_input_grad[1])
+        g = g.contiguous()
+        dA = dB = None
+        if dyn is None and ctx.deterministic and rows.numel():
+            dyn = DynGraph(rows, cols, A.shape[0], B.shape[0])
+        if dyn is not None:
+            # the two sums as SpMMs over the edge list's CSR forms: CSR order, long rows on the chunk plan, no atomics
+            if want_a:
+                dyn.fwd.vals = g[dyn.perm].contiguous()
+                dA = spmm_raw(dyn.fwd, B, Y=torch.empty(dyn.n_rows, A.shape[1], dtype=torch.float32, device=A.device))
+            if want_b:
+                dyn.bwd.vals = g[dyn.perm_t].contiguous()
+                dB = spmm_raw(dyn.bwd, A, Y=torch.empty(dyn.n_cols, A.shape[1], dtype=torch.float32, device=A.device))
+            if same:
+                return (dA + dB if want_a else None), None, None, None, None
+            return dA, dB, None, None, None
+        if want_a:
+            dA = torch.zeros_like(A)
+        if same:
+            dB = dA
+        elif want_b:
+            dB = torch.zeros_like(B)
+        if want_a or want_b:
+            _lib.check(_lib.load().mmrec_edge_dot_bwd_f32(_p(g), _p(A), A.shape[0], _p(B), B.shape[0], _p(rows), _p(cols),
+                                                          rows.numel(), A.shape[1], _p(dA), _p(dB), _stream()), "edge_dot_bwd")
+        return dA, (None if same else dB), None, None, None
+
+
+def edge_dot(A, B, rows, cols, dyn=None):
+    """out[e] = <A[rows[e]], B[cols[e]]> -- one dot product per edge (SDDMM): LATTICE's learned similarities of the kNN pairs
+    (lattice.py:141,146 restricted to the kept pairs), GRCN's edge scores (grcn.py:63) -- WITHOUT the two [n_edges, d] gathered
+    copies; differentiable in A and B.
+    Served by the kernels (`edge_dot_served`): device fp32 contiguous tables of one width among 8 / 16 / 32 / 64 k <= 384, int64
+    device ids, `EDGE_DOT` on.  There an id outside its table (-1 = "no edge") gives 0, adds nothing to the gradients and is
+    never used as an address.  The forward's bits repeat run after run.  The backward is
+      * with `dyn` (a DynGraph over EXACTLY these rows, cols -- n_rows = len(A), n_cols = len(B)), or under `DETERMINISTIC`
+        (a DynGraph is then built): dA = spmm_raw(dyn.fwd with values g[dyn.perm], B), dB = spmm_raw(dyn.bwd with values
+        g[dyn.perm_t], A) -- CSR order, long rows on the SpMM's chunk plan, no atomics: fixed bits, and a hub's gradient row is
+        not thousands of contended atomics;
+      * otherwise mmrec_edge_dot_bwd_f32: fp32 atomics into zeroed buffers (the last ulp depends on arrival order).
+    `A is B`: the two gradients are summed.
+    EVERY OTHER CASE (CPU tensors, other widths or dtypes, non-contiguous operands, the switch off) is the torch composition
+    `(A[rows] * B[cols]).sum(-1)` with stock autograd: a fallback to the two-step form, not a CPU path of the kernel."""
+    if edge_dot_served(A, B, rows, cols):
+        return _EdgeDot.apply(A, None if A is B else B, rows, cols, dyn)
+    return (A[rows] * B[cols]).sum(-1)
 
 
 # ------------------------------------------------------------------------------------------------

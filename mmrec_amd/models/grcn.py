@@ -5,7 +5,8 @@ Per modality a content GCN scores every user-item edge by attention -- softmax o
 per-node confidence and pruned by relu(max), then weight a two-hop sum aggregation of the id embeddings.  Every
 aggregation is the CSR SpMM with DIFFERENTIABLE per-edge values (`hip_ops.spmm_vals`: forward, d/dX through the
 transposed structure, d/dvalues as per-edge dot products) over one structure built once -- the bidirectional edge
-list never changes; the per-edge scores and the segment softmax are row-wise gathers / scatters in torch.  BPR runs
+list never changes; the per-edge scores are the SDDMM kernel (`hip_ops.edge_dot`, its backward the same SpMM over that
+structure), the segment softmax is row-wise gathers / scatters in torch.  BPR runs
 on the fused kernel over the 192-wide concatenation, evaluation on the fused score + mask + top-K.
 
 Reference behaviour kept:
@@ -65,7 +66,7 @@ class CGCN(nn.Module):
         for _ in range(self.num_routing):
             preference = F.normalize(preference)          # + the all-zero user rows of the item-side aggregation
         x = torch.cat((preference, features), dim=0)
-        score = (x[edges.dst] * x[edges.src]).sum(dim=-1)
+        score = hip_ops.edge_dot(x, x, edges.dst, edges.src, dyn=edges.dyn)
         alpha = segment_softmax(score, edges.dst, x.shape[0])
         return x + hip_ops.spmm_vals(edges.dyn, x, alpha), alpha
 

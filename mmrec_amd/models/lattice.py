@@ -127,7 +127,7 @@ class LATTICE(RelabelledIdsMixin, AdjacentTablesMixin, FusedEvalMixin, GeneralRe
         build_knn_neighbourhood (utils/utils.py:119-137) without the dense matrix."""
         fn = feats.div(torch.norm(feats, p=2, dim=-1, keepdim=True))
         rows, cols = self._knn_pairs(fn, in_dataset_ids)
-        return rows, cols, (fn[rows] * fn[cols]).sum(-1)
+        return rows, cols, hip_ops.edge_dot(fn, fn, rows, cols)
 
     def _original_graph(self, raw_feats, cache):
         """Frozen per-modality graph.  The reference caches it as a dense [I, I] tensor

@@ -364,6 +364,35 @@ int mmrec_edge_dot_bwd_f32(const float* g, const float* A, int64_t n_a, const fl
                            const int64_t* rows, const int64_t* cols, int64_t n_edges, int32_t d,
                            float* dA, float* dB, mmrec_stream_t stream);
 
+/* Segment softmax over the edges that share a node, and its backward -- the step between mmrec_edge_dot_f32 and the product
+ * with learned values.  ADDITIVE to ABI 16: three new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: torch_geometric.utils.softmax(alpha, index) -- grcn.py:69 (scatter-max, gathers, exp, scatter-add, divide).
+ * Segments are the rows of a CSR rowptr [n_rows + 1] (device, int32).  Entry j of row r, rowptr[r] <= j < rowptr[r + 1], lives
+ * at position p = perm ? perm[j] : j of score / out / alpha / g / ds [n_edges]: input and output are in the caller's (COO)
+ * order, like mmrec_edge_dot_f32's.  perm [n_edges] int64 (device), NULL = identity; a position outside [0, n_edges) is skipped
+ * and never used as an address.
+ *   forward   out[p] = exp(s[p] - m_r) / (sum_q exp(s[q] - m_r) + eps),  m_r = max_q s[q] over row r
+ *   backward  ds[p]  = alpha[p] * (g[p] - sum_q alpha[q] g[q])  -- reads the forward's result, not the scores; the exact
+ *             derivative of the forward with the maximum detached; WRITES ds, does not add into it.
+ * Rows of at most mmrec_segment_softmax_group_max() entries: one 16-lane group per row; longer rows: one workgroup per row,
+ * taken from long_rows [n_long] (device, int32, ascending) -- exactly the rows longer than that constant, which is what
+ * mmrec_spmm_plan_fill writes when called with the constant as its threshold.  A list that names other rows than those leaves
+ * entries of out unwritten (a device list cannot be checked here; hip_ops checks it on the host when it builds it).
+ * n_long == 0 (long_rows may be NULL): the 16-lane groups serve every row, whatever its length.
+ * No atomics, every sum in an order fixed by the row's length: both directions repeat bit for bit.  Empty rows write nothing.
+ * A row that holds a NaN, a +inf or nothing but -inf is NaN in every entry and no other row is affected; a -inf entry next to
+ * a finite maximum is exactly 0.  out must not be score, ds must not be alpha or g.
+ * Negative sizes: MMREC_ERR_BAD_ARG; n_edges == 0 or n_rows == 0: 0 and no launch (pointers may be NULL); n_edges > 2^31 - 1:
+ * MMREC_ERR_UNSUPPORTED; NULL rowptr / score / out (alpha / g / ds): MMREC_ERR_BAD_ARG; n_long > 0 with NULL long_rows:
+ * MMREC_ERR_BAD_ARG -- in this order, before any launch.  No synchronisation, no allocation, capture-safe, no global state. */
+int32_t mmrec_segment_softmax_group_max(void);
+int mmrec_segment_softmax_f32(const int32_t* rowptr, int32_t n_rows, const int64_t* perm, const int32_t* long_rows,
+                              int32_t n_long, const float* score, int64_t n_edges, float eps, float* out,
+                              mmrec_stream_t stream);
+int mmrec_segment_softmax_bwd_f32(const int32_t* rowptr, int32_t n_rows, const int64_t* perm, const int32_t* long_rows,
+                                  int32_t n_long, const float* alpha, const float* g, int64_t n_edges, float* ds,
+                                  mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

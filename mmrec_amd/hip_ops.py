@@ -1901,6 +1901,109 @@ def edge_dot(A, B, rows, cols, dyn=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# Softmax over the edges that share a node (mmrec_segment_softmax_*): between edge_dot and spmm_vals
+# ------------------------------------------------------------------------------------------------
+EDGE_SOFTMAX = True   # False: every edge_softmax call is the scatter / gather composition (A/B runs)
+
+
+def segment_softmax_torch(score, index, n, eps=1e-16):
+    """torch_geometric.utils.softmax: softmax over the entries sharing an index (eps in the denominator) -- the composition
+    `edge_softmax` falls back to, and what GRCN ran before the kernel."""
+    mx = torch.full((n,), float('-inf'), dtype=score.dtype, device=score.device)
+    mx = mx.scatter_reduce(0, index, score.detach(), 'amax', include_self=True)
+    e = (score - mx[index]).exp()
+    den = torch.zeros(n, dtype=score.dtype, device=score.device).index_add_(0, index, e)
+    return e / (den[index] + eps)
+
+
+def segment_softmax_group_max():
+    """rows longer than this go to one workgroup each (the library's constant)"""
+    return int(_lib.load().mmrec_segment_softmax_group_max())
+
+
+def segment_long_rows(rowptr_host):
+    """The rows (int32, ascending, host) of a CSR rowptr that are longer than `segment_softmax_group_max()`: the SpMM's plan
+    helper at that threshold.  Checked here against the lengths: the library cannot check a device list, and a list that
+    disagrees with the kernel's constant would leave rows of the output unwritten."""
+    lib = _lib.load()
+    rp = np.ascontiguousarray(rowptr_host, dtype=np.int32)
+    n_rows, thr = rp.size - 1, segment_softmax_group_max()
+    n_long, n_chunks = ctypes.c_int32(0), ctypes.c_int32(0)
+    ptr = rp.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(lib.mmrec_spmm_plan_count(ptr, n_rows, thr, ctypes.byref(n_long), ctypes.byref(n_chunks)), "spmm_plan_count")
+    lr, cp = np.empty(n_long.value, dtype=np.int32), np.empty(n_long.value + 1, dtype=np.int32)
+    if n_long.value:
+        _lib.check(lib.mmrec_spmm_plan_fill(ptr, n_rows, thr, lr.ctypes.data_as(ctypes.c_void_p),
+                                            cp.ctypes.data_as(ctypes.c_void_p)), "spmm_plan_fill")
+    want = np.flatnonzero(np.diff(rp.astype(np.int64)) > thr).astype(np.int32)
+    if not np.array_equal(lr, want):
+        raise _lib.MMRecHipError("segment softmax: the plan's long rows are not the rows longer than %d" % thr)
+    return lr
+
+
+def _softmax_side(dyn, by):
+    """(CsrGraph, perm, long_rows or None) of one direction; the long-row list is built once per DynGraph and direction"""
+    if by not in ("row", "col"):
+        raise ValueError("edge_softmax: by must be 'row' or 'col', got %r" % (by,))
+    g, perm = (dyn.fwd, dyn.perm) if by == "row" else (dyn.bwd, dyn.perm_t)
+    cache = dyn.__dict__.setdefault("_softmax_long", {})
+    if by not in cache:
+        lr = segment_long_rows(g.rowptr_host)
+        cache[by] = torch.from_numpy(lr).to(g.rowptr.device) if lr.size else None
+    return g, perm, cache[by]
+
+
+def edge_softmax_served(score, dyn):
+    """True where `edge_softmax` runs the kernels: a contiguous 1-D fp32 device tensor with one entry per edge of `dyn`, and
+    the `EDGE_SOFTMAX` switch on."""
+    return bool(EDGE_SOFTMAX and isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float32 and
+                score.dim() == 1 and score.is_contiguous() and score.numel() == dyn.rows.numel())
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, score, dyn, by, eps):
+        g, perm, long_rows = _softmax_side(dyn, by)
+        n_long = 0 if long_rows is None else long_rows.numel()
+        alpha = torch.empty_like(score)
+        _lib.check(_lib.load().mmrec_segment_softmax_f32(_p(g.rowptr), g.n_rows, _p(perm), _p(long_rows), n_long, _p(score),
+                                                         score.numel(), eps, _p(alpha), _stream()), "segment_softmax")
+        ctx.dyn, ctx.by = dyn, by
+        ctx.save_for_backward(alpha)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, grad):
+        (alpha,) = ctx.saved_tensors
+        g, perm, long_rows = _softmax_side(ctx.dyn, ctx.by)
+        n_long = 0 if long_rows is None else long_rows.numel()
+        grad = grad.contiguous()
+        ds = torch.empty_like(alpha)
+        _lib.check(_lib.load().mmrec_segment_softmax_bwd_f32(_p(g.rowptr), g.n_rows, _p(perm), _p(long_rows), n_long,
+                                                             _p(alpha), _p(grad), alpha.numel(), _p(ds), _stream()),
+                   "segment_softmax_bwd")
+        return ds, None, None, None
+
+
+def edge_softmax(score, dyn, by="row", eps=1e-16):
+    """Softmax of one score per edge over the edges that share `dyn.rows` (by="row") or `dyn.cols` (by="col"):
+    alpha[e] = exp(s[e] - m) / (sum exp(s - m) + eps) with m the maximum of e's segment -- torch_geometric.utils.softmax, GRCN's
+    attention weights (grcn.py:69).  Input and output are in the order of dyn's edge list; differentiable in `score`
+    (d s[e] = alpha[e] (g[e] - sum alpha g) over the segment, from the saved alpha).
+    Served by the kernels (`edge_softmax_served`): one launch forward, one backward (+ one each for the rows longer than
+    `segment_softmax_group_max()`), over the CSR form the DynGraph already holds; no atomics, so both directions repeat bit
+    for bit, with or without `DETERMINISTIC`.  A segment that holds a NaN, a +inf or nothing but -inf is NaN in every entry.
+    EVERY OTHER CASE (CPU tensors, other dtypes, non-contiguous scores, the switch off) is `segment_softmax_torch` with stock
+    autograd: the composition of scatter-max, gathers, exp, index_add and a division."""
+    if edge_softmax_served(score, dyn):
+        return _EdgeSoftmax.apply(score, dyn, by, float(eps))
+    if by not in ("row", "col"):
+        raise ValueError("edge_softmax: by must be 'row' or 'col', got %r" % (by,))
+    index, n = (dyn.rows, dyn.n_rows) if by == "row" else (dyn.cols, dyn.n_cols)
+    return segment_softmax_torch(score, index, n, eps)
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

@@ -6,8 +6,9 @@ per-node confidence and pruned by relu(max), then weight a two-hop sum aggregati
 aggregation is the CSR SpMM with DIFFERENTIABLE per-edge values (`hip_ops.spmm_vals`: forward, d/dX through the
 transposed structure, d/dvalues as per-edge dot products) over one structure built once -- the bidirectional edge
 list never changes; the per-edge scores are the SDDMM kernel (`hip_ops.edge_dot`, its backward the same SpMM over that
-structure), the segment softmax is row-wise gathers / scatters in torch.  BPR runs
-on the fused kernel over the 192-wide concatenation, evaluation on the fused score + mask + top-K.
+structure), the segment softmax over a target's incoming edges is `hip_ops.edge_softmax` over the same structure's CSR
+form (no atomics: the attention weights and their gradient repeat bit for bit).  BPR runs on the fused kernel over the 192-wide concatenation, evaluation on the fused score + mask +
+top-K.
 
 Reference behaviour kept:
   * the routing loop calls the attention layer on the user -> item edges only, so nothing is ever aggregated AT a
@@ -27,12 +28,9 @@ from mmrec_amd.models.mmgcn import _lin64
 
 
 def segment_softmax(score, index, n):
-    """torch_geometric.utils.softmax: softmax over the entries sharing an index (eps 1e-16 in the denominator)"""
-    mx = torch.full((n,), float('-inf'), dtype=score.dtype, device=score.device)
-    mx = mx.scatter_reduce(0, index, score.detach(), 'amax', include_self=True)
-    e = (score - mx[index]).exp()
-    den = torch.zeros(n, dtype=score.dtype, device=score.device).index_add_(0, index, e)
-    return e / (den[index] + 1e-16)
+    """torch_geometric.utils.softmax: softmax over the entries sharing an index (eps 1e-16 in the denominator) -- the torch
+    composition; the model itself calls `hip_ops.edge_softmax` over its edge structure"""
+    return hip_ops.segment_softmax_torch(score, index, n)
 
 
 class EGCN(nn.Module):
@@ -67,7 +65,7 @@ class CGCN(nn.Module):
             preference = F.normalize(preference)          # + the all-zero user rows of the item-side aggregation
         x = torch.cat((preference, features), dim=0)
         score = hip_ops.edge_dot(x, x, edges.dst, edges.src, dyn=edges.dyn)
-        alpha = segment_softmax(score, edges.dst, x.shape[0])
+        alpha = hip_ops.edge_softmax(score, edges.dyn)
         return x + hip_ops.spmm_vals(edges.dyn, x, alpha), alpha
 
 

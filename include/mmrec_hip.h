@@ -393,6 +393,35 @@ int mmrec_segment_softmax_bwd_f32(const int32_t* rowptr, int32_t n_rows, const i
                                   int32_t n_long, const float* alpha, const float* g, int64_t n_edges, float* ds,
                                   mmrec_stream_t stream);
 
+/* Fused edge attention ("GAT aggregation"): the scores, the softmax over a row's edges and the weighted sum in one pass --
+ * mmrec_edge_dot_f32 -> mmrec_segment_softmax_f32 -> mmrec_spmm_csr_f32 with values, with every source row gathered once.
+ * ADDITIVE to ABI 16: two new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: the attention layer of the content GCN -- grcn.py:63-72 (x_i . x_j per edge, softmax over the edges of a target,
+ *           the weighted sum of the source rows).
+ * Rows are the rows of a CSR (rowptr [n_rows + 1], colidx [n_edges], device, int32); slot j of row r lives at position
+ * p = perm ? perm[j] : j of alpha [n_edges] (the caller's COO order; perm as for mmrec_segment_softmax_f32).
+ *   s_p     = <Q[r], KV[colidx[j]]>                                     Q [n_q, 64], KV [n_kv, 64] fp32 row-major, n_q >= n_rows
+ *   alpha_p = exp(s_p - m_r) / (sum_q exp(s_q - m_r) + eps),            m_r = max over the row
+ *   Y[r]    = sum_p alpha_p * KV[colidx[j]]                             Y [n_rows, 64]
+ * Q == KV is allowed; Y and alpha must not alias an input.  d == 64 only.  Rows of at most mmrec_edge_attention_group_max()
+ * entries: one 16-lane group per row with an online (running-maximum) softmax; longer rows: one workgroup per row of long_rows
+ * [n_long] (device, int32) -- the rows longer than that constant as mmrec_spmm_plan_fill lists them at that threshold; the
+ * constant equals mmrec_segment_softmax_group_max(), so one list serves both.  n_long == 0: the groups serve every row.  A list
+ * that names other rows leaves rows of Y unwritten (hip_ops checks it on the host).
+ * EVERY row of Y is written (zeros for a row without edges).  A colidx outside [0, n_kv) or a position outside [0, n_edges) is
+ * an absent edge: never an address, adds nothing, its alpha is not written.  No atomics: the bits of Y and alpha are a
+ * function of the inputs and the row lengths.  A row whose scores hold a NaN, a +inf or nothing but -inf is NaN in every
+ * alpha and in Y[r]; no other row is affected; a -inf score next to a finite maximum weighs exactly 0.
+ * d != 64: MMREC_ERR_UNSUPPORTED; negative sizes: MMREC_ERR_BAD_ARG; n_rows == 0 or n_edges == 0: 0 and no launch (pointers
+ * may be NULL; with rows and no edges Y is NOT written: the caller's zeros); n_edges or n_kv > 2^31 - 1: MMREC_ERR_UNSUPPORTED;
+ * n_q < n_rows, a NULL rowptr / colidx / Q / KV / Y / alpha, n_long > 0 with NULL long_rows: MMREC_ERR_BAD_ARG -- in this
+ * order, before any launch.  No synchronisation, no allocation, capture-safe, no global state. */
+int32_t mmrec_edge_attention_group_max(void);
+int mmrec_edge_attention_f32(const int32_t* rowptr, int32_t n_rows, const int32_t* colidx, const int64_t* perm,
+                             const int32_t* long_rows, int32_t n_long, const float* Q, int64_t n_q, const float* KV,
+                             int64_t n_kv, int32_t d, int64_t n_edges, float eps, float* Y, float* alpha,
+                             mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

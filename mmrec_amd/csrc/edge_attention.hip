@@ -1,0 +1,210 @@
+// Fused edge attention: scores, softmax over a target's incoming edges and the weighted sum in ONE pass over the edges
+// (include/mmrec_hip.h, additive to ABI 16).  For row r of a CSR (rowptr, colidx), slot j at position p = perm ? perm[j] : j of the
+// caller's (COO) arrays, exactly as in edge_softmax.hip:
+//     s_p = <Q[r], KV[colidx[j]]>,   alpha_p = exp(s_p - m_r) / (sum_q exp(s_q - m_r) + eps),   Y[r] = sum_p alpha_p KV[colidx[j]]
+// which was edge_dot -> segment softmax -> SpMM with values: KV[colidx[j]] gathered twice, the scores and the weights each
+// written and read back.  Here every source row is gathered ONCE and serves the dot product and the sum.
+//
+// One 16-lane group owns a row (the access shape of spmm.hip: lane t holds the float4 of columns 4 t ... 4 t + 3 of q, of the
+// gathered row and of the accumulator).  A score is 4 roundings in the lane's chain (f4_dot) and 4 in the row16_sum butterfly.
+// The softmax is online: the group keeps (m, den, acc); a score above m first multiplies den and acc by exp(m - s), then every
+// score adds e = exp(s - m) to den and e * row to acc; a score of -inf has e = 0.
+//   group  four rows per wave, 16 per workgroup; rows of at most ATT_GROUP_MAX entries, or every row when no list is given.
+//   block  one 256-thread workgroup per LISTED row (the list of mmrec_spmm_plan_fill at ATT_GROUP_MAX, which equals the segment
+//          softmax's constant: one list serves both): group g takes the slots 16 g ... 16 g + 15 of every 256, with its own
+//          state; the 16 states go through LDS and are combined in the order g = 0 ... 15 by weights exp(m_g - max m).
+// alpha in the caller's order: lane t of the group that handles slots base ... base + 15 PARKS the raw score of slot base + t in
+// alpha[p]; after the row the same lane reads it back and writes exp(s - m) / (den + eps) -- written and re-read by one lane,
+// so no fence (edge_softmax.hip's rule).  No atomics: the bits of Y and alpha are a function of the inputs and the row lengths.
+// A colidx outside [0, n_kv) or a position outside [0, n_edges) is an absent edge: never an address, adds nothing, its alpha
+// stays unwritten.  EVERY row of Y is written: zeros for a row without (present) edges.  Non-finite scores follow the
+// arithmetic: fmaxf skips a NaN, which then enters den and acc through exp; +inf gives exp(inf - inf) = NaN; a row of nothing
+// but -inf has no maximum and is set to NaN (exp(-inf + inf) in its alphas): such a row is NaN in every alpha and in Y[r], no
+// other row is touched, and a -inf next to a finite maximum is exactly 0.
+#include "common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int ATT_BLOCK = 256;
+constexpr int ATT_GROUP = 16;                   // lanes per row: 64 columns as float4
+constexpr int ATT_GROUPS = ATT_BLOCK / ATT_GROUP;
+constexpr int ATT_GROUP_MAX = 256;              // = edge_softmax.hip's SEG_GROUP_MAX: a DynGraph's long-row list serves both
+constexpr int ATT_NB = 4;                       // gathers in flight per group and step
+constexpr int ATT_MAX_BLOCKS = 2048;            // 8 resident 256-thread workgroups on each of 256 CUs; the loop strides the rest
+
+struct RowState {
+    float m, den;
+    float4 acc;
+    bool any;                                   // a present edge was seen (uniform over the group)
+};
+
+// position of CSR slot j in the caller's arrays, -1 where it lies outside them
+__device__ __forceinline__ int att_pos(const int64_t* __restrict__ perm, int j, int n_edges) {
+    if (!perm) return j;
+    const int64_t p = perm[j];
+    return (p >= 0 && p < n_edges) ? (int)p : -1;
+}
+
+// The slots first ... first + 15, first + stride ..., below end, of one row for one 16-lane group: raw scores parked in alpha,
+// the online state updated.  Trip counts and branches are uniform over the group (the shuffles and butterflies need that).
+__device__ __forceinline__ void attend_span(int first, int end, int stride, int t, const int32_t* __restrict__ colidx,
+                                            const int64_t* __restrict__ perm, int n_edges, float4 q,
+                                            const float4* __restrict__ KV4, int n_kv, float* __restrict__ alpha, RowState& st) {
+    for (int base = first; base < end; base += stride) {
+        const int j = base + t;
+        int c = -1, p = -1;
+        if (j < end) {
+            c = colidx[j];
+            p = att_pos(perm, j, n_edges);
+            if (c < 0 || c >= n_kv || p < 0) c = -1;          // an absent edge
+        }
+        const int cnt = min(ATT_GROUP, end - base);
+        float mine = 0.f;
+        for (int k0 = 0; k0 < cnt; k0 += ATT_NB) {
+            float4 x[ATT_NB];
+            int cs[ATT_NB];
+#pragma unroll
+            for (int u = 0; u < ATT_NB; ++u) {
+                cs[u] = __shfl(c, k0 + u, ATT_GROUP);           // (-1 beyond cnt: those lanes hold -1)
+                x[u] = cs[u] >= 0 ? KV4[(size_t)cs[u] * ATT_GROUP + t] : f4_zero();
+            }
+#pragma unroll
+            for (int u = 0; u < ATT_NB; ++u) {
+                const float s = row16_sum(f4_dot(q, x[u]));
+                if (cs[u] < 0) continue;
+                st.any = true;
+                if (t == k0 + u) mine = s;
+                if (s > st.m) {                                 // a new maximum: rescale what was summed under the old one
+                    const float sc = expf(st.m - s);            // (m = -inf: 0, and den = acc = 0)
+                    st.den *= sc;
+                    st.acc = f4_scale(sc, st.acc);
+                    st.m = s;
+                }
+                const float e = s == -INFINITY ? 0.f : expf(s - st.m);     // (-inf before any maximum: not exp(-inf + inf))
+                st.den += e;
+                st.acc = f4_fma(e, x[u], st.acc);
+            }
+        }
+        if (c >= 0) alpha[p] = mine;                            // parked: this lane reads it back in write_alpha
+    }
+}
+
+// the lane that parked a slot's score turns it into the weight
+__device__ __forceinline__ void write_alpha(int first, int end, int stride, const int32_t* __restrict__ colidx,
+                                            const int64_t* __restrict__ perm, int n_edges, int n_kv, float m, float dn,
+                                            float* __restrict__ alpha) {
+    for (int j = first; j < end; j += stride) {
+        const int c = colidx[j];
+        const int p = att_pos(perm, j, n_edges);
+        if (c >= 0 && c < n_kv && p >= 0) alpha[p] = expf(alpha[p] - m) / dn;
+    }
+}
+
+// den + eps; NaN for a row whose present scores are all -inf (no maximum)
+__device__ __forceinline__ float att_denominator(float m, float den, float eps) {
+    return m == -INFINITY ? __int_as_float(0x7fc00000) : den + eps;
+}
+
+__device__ __forceinline__ void att_span(const int32_t* __restrict__ rowptr, int r, int n_edges, int& start, int& end) {
+    start = rowptr[r];
+    end = rowptr[r + 1];
+    if (start < 0) start = 0;
+    if (end > n_edges) end = n_edges;
+}
+
+__global__ __launch_bounds__(ATT_BLOCK) void edge_attention_group_kernel(
+    const int32_t* __restrict__ rowptr, int n_rows, const int32_t* __restrict__ colidx, const int64_t* __restrict__ perm,
+    bool skip_long, const float4* __restrict__ Q4, const float4* __restrict__ KV4, int n_kv, int n_edges, float eps,
+    float4* __restrict__ Y4, float* __restrict__ alpha) {
+    const int t = threadIdx.x % ATT_GROUP;
+    const int stride = gridDim.x * ATT_GROUPS;
+    for (long r = (long)blockIdx.x * ATT_GROUPS + threadIdx.x / ATT_GROUP; r < n_rows; r += stride) {
+        int start, end;
+        att_span(rowptr, (int)r, n_edges, start, end);
+        if (skip_long && end - start > ATT_GROUP_MAX) continue;            // the block kernel's
+        RowState st{-INFINITY, 0.f, f4_zero(), false};
+        if (end > start)
+            attend_span(start, end, ATT_GROUP, t, colidx, perm, n_edges, Q4[(size_t)r * ATT_GROUP + t], KV4, n_kv, alpha, st);
+        if (!st.any) {
+            Y4[(size_t)r * ATT_GROUP + t] = f4_zero();
+            continue;
+        }
+        const float dn = att_denominator(st.m, st.den, eps);
+        Y4[(size_t)r * ATT_GROUP + t] = make_float4(st.acc.x / dn, st.acc.y / dn, st.acc.z / dn, st.acc.w / dn);
+        write_alpha(start + t, end, ATT_GROUP, colidx, perm, n_edges, n_kv, st.m, dn, alpha);
+    }
+}
+
+__global__ __launch_bounds__(ATT_BLOCK) void edge_attention_block_kernel(
+    const int32_t* __restrict__ rowptr, int n_rows, const int32_t* __restrict__ colidx, const int64_t* __restrict__ perm,
+    const int32_t* __restrict__ long_rows, const float4* __restrict__ Q4, const float4* __restrict__ KV4, int n_kv, int n_edges,
+    float eps, float* __restrict__ Y, float* __restrict__ alpha) {
+    __shared__ float s_m[ATT_GROUPS], s_den[ATT_GROUPS], s_any[ATT_GROUPS];
+    __shared__ float4 s_acc[ATT_GROUPS][ATT_GROUP];
+    const int r = long_rows[blockIdx.x];
+    if (r < 0 || r >= n_rows) return;                                      // (the whole workgroup)
+    int start, end;
+    att_span(rowptr, r, n_edges, start, end);
+    const int t = threadIdx.x % ATT_GROUP, g = threadIdx.x / ATT_GROUP;
+    RowState st{-INFINITY, 0.f, f4_zero(), false};
+    attend_span(start + g * ATT_GROUP, end, ATT_BLOCK, t, colidx, perm, n_edges, Q4[(size_t)r * ATT_GROUP + t], KV4, n_kv, alpha, st);
+    if (t == 0) {
+        s_m[g] = st.m;
+        s_den[g] = st.den;
+        s_any[g] = st.any ? 1.f : 0.f;
+    }
+    s_acc[g][t] = st.acc;
+    __syncthreads();
+    // every thread: the row's maximum, and the 16 denominators under it, added in the order g = 0 ... 15
+    float m = -INFINITY, den = 0.f;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < ATT_GROUPS; ++k) {
+        m = fmaxf(m, s_m[k]);
+        any = any || s_any[k] != 0.f;
+    }
+    float w[ATT_GROUPS];
+#pragma unroll
+    for (int k = 0; k < ATT_GROUPS; ++k) {
+        w[k] = s_m[k] == m ? 1.f : expf(s_m[k] - m);                       // (equal infinities: 1, not exp(inf - inf))
+        den = fmaf(s_den[k], w[k], den);
+    }
+    const float dn = att_denominator(m, den, eps);
+    if (threadIdx.x < 4 * ATT_GROUP) {                                     // the first wave: one column of Y[r] per lane
+        const float* col = reinterpret_cast<const float*>(&s_acc[0][0]) + threadIdx.x;
+        float y = 0.f;
+#pragma unroll
+        for (int k = 0; k < ATT_GROUPS; ++k) y = fmaf(col[k * 4 * ATT_GROUP], w[k], y);
+        Y[(size_t)r * (4 * ATT_GROUP) + threadIdx.x] = any ? y / dn : 0.f;
+    }
+    if (any) write_alpha(start + threadIdx.x, end, ATT_BLOCK, colidx, perm, n_edges, n_kv, m, dn, alpha);
+}
+
+}  // namespace
+
+extern "C" int32_t mmrec_edge_attention_group_max(void) { return ATT_GROUP_MAX; }
+
+extern "C" int mmrec_edge_attention_f32(const int32_t* rowptr, int32_t n_rows, const int32_t* colidx, const int64_t* perm,
+                                        const int32_t* long_rows, int32_t n_long, const float* Q, int64_t n_q, const float* KV,
+                                        int64_t n_kv, int32_t d, int64_t n_edges, float eps, float* Y, float* alpha,
+                                        mmrec_stream_t stream) {
+    if (d != 4 * ATT_GROUP) return MMREC_ERR_UNSUPPORTED;
+    if (n_rows < 0 || n_edges < 0 || n_long < 0 || n_q < 0 || n_kv < 0) return MMREC_ERR_BAD_ARG;
+    if (n_rows == 0 || n_edges == 0) return 0;                             // nothing to launch (the caller's Y is all zeros)
+    if (n_edges > INT32_MAX || n_kv > INT32_MAX) return MMREC_ERR_UNSUPPORTED;
+    if (n_q < n_rows) return MMREC_ERR_BAD_ARG;                            // one row of Q per row of the CSR
+    if (!rowptr || !colidx || !Q || !KV || !Y || !alpha) return MMREC_ERR_BAD_ARG;
+    if (n_long > 0 && !long_rows) return MMREC_ERR_BAD_ARG;
+    hipStream_t s = mmrec_stream(stream);
+    const int blocks = (n_rows + ATT_GROUPS - 1) / ATT_GROUPS;
+    hipLaunchKernelGGL(edge_attention_group_kernel, dim3(blocks < ATT_MAX_BLOCKS ? blocks : ATT_MAX_BLOCKS), dim3(ATT_BLOCK), 0, s,
+                       rowptr, (int)n_rows, colidx, perm, n_long > 0, reinterpret_cast<const float4*>(Q),
+                       reinterpret_cast<const float4*>(KV), (int)n_kv, (int)n_edges, eps, reinterpret_cast<float4*>(Y), alpha);
+    if (n_long > 0)
+        hipLaunchKernelGGL(edge_attention_block_kernel, dim3(n_long), dim3(ATT_BLOCK), 0, s, rowptr, (int)n_rows, colidx, perm,
+                           long_rows, reinterpret_cast<const float4*>(Q), reinterpret_cast<const float4*>(KV), (int)n_kv,
+                           (int)n_edges, eps, Y, alpha);
+    MMREC_RETURN_LAUNCH_STATUS();
+}

@@ -2004,6 +2004,116 @@ def edge_softmax(score, dyn, by="row", eps=1e-16):
 
 
 # ------------------------------------------------------------------------------------------------
+# Fused edge attention (mmrec_edge_attention_f32): edge_dot -> edge_softmax -> spmm_vals in one pass over the edges
+# ------------------------------------------------------------------------------------------------
+EDGE_ATTENTION = True   # False: every edge_attention call is the three-op composition (A/B runs)
+
+
+def edge_attention_group_max():
+    """rows longer than this go to one workgroup each (the library's constant; equal to `segment_softmax_group_max()`)"""
+    return int(_lib.load().mmrec_edge_attention_group_max())
+
+
+def _attention_long_rows(dyn):
+    """the long-row list (device int32, or None) of dyn's row side: built on the host once per DynGraph and checked against the
+    row lengths (`segment_long_rows`).  The attention kernel's threshold is the softmax's, so it is the softmax's cached list;
+    a library in which the two constants differ is refused rather than served a list cut at the wrong length."""
+    if edge_attention_group_max() != segment_softmax_group_max():
+        raise _lib.MMRecHipError("edge attention: group maximum %d is not the segment softmax's %d"
+                                 % (edge_attention_group_max(), segment_softmax_group_max()))
+    return _softmax_side(dyn, "row")[2]
+
+
+def edge_attention_served(Q, KV, dyn):
+    """True where `edge_attention` runs the kernel: device fp32 contiguous [*, 64] tables with one row of Q per row of `dyn`
+    and one row of KV per column, and the `EDGE_ATTENTION` switch on.  `Q is KV` is allowed."""
+    def table(t, n):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
+                t.shape[1] == EMB_DIM and t.is_contiguous() and t.shape[0] == n)
+    return bool(EDGE_ATTENTION and table(Q, dyn.n_rows) and table(KV, dyn.n_cols))
+
+
+def _spmm_with(g, vals, X):
+    g.vals = vals
+    return spmm_raw(g, X, Y=torch.empty(g.n_rows, X.shape[1], dtype=torch.float32, device=X.device))
+
+
+class _EdgeAttention(torch.autograd.Function):
+    """forward(Q, KV or None for `Q is KV`, dyn, eps) -> (Y, alpha)"""
+
+    @staticmethod
+    def forward(ctx, Q, KV, dyn, eps):
+        ctx.same = KV is None
+        if ctx.same:
+            KV = Q
+        g, n_edges = dyn.fwd, dyn.rows.numel()
+        long_rows = _attention_long_rows(dyn)
+        n_long = 0 if long_rows is None else long_rows.numel()
+        # every row of Y is the kernel's to write -- unless there is no edge, and then no launch
+        Y = (torch.empty if n_edges else torch.zeros)(dyn.n_rows, EMB_DIM, dtype=torch.float32, device=Q.device)
+        alpha = torch.empty(n_edges, dtype=torch.float32, device=Q.device)
+        _lib.check(_lib.load().mmrec_edge_attention_f32(_p(g.rowptr), g.n_rows, _p(g.colidx), _p(dyn.perm), _p(long_rows), n_long,
+                                                        _p(Q), Q.shape[0], _p(KV), KV.shape[0], EMB_DIM, n_edges, eps, _p(Y),
+                                                        _p(alpha), _stream()), "edge_attention")
+        ctx.dyn = dyn
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(Q, KV, alpha)
+        return Y, alpha
+
+    @staticmethod
+    def backward(ctx, dY, dA):
+        Q, KV, alpha = ctx.saved_tensors
+        dyn, same = ctx.dyn, ctx.same
+        want_q, want_kv = ctx.needs_input_grad[0], (ctx.needs_input_grad[0] if same else ctx.needs_input_grad[1])
+        if (dY is None and dA is None) or not (want_q or want_kv) or not alpha.numel():
+            zq = torch.zeros_like(Q) if want_q else None
+            return zq, (None if same or not want_kv else torch.zeros_like(KV)), None, None
+        # d alpha_e = <dY[row_e], KV[col_e]> (+ what arrives at alpha itself); through the softmax from the saved alpha
+        g = None
+        if dY is not None:
+            dY = dY.contiguous()
+            g = _edge_dot_fwd(dY, KV, dyn.rows, dyn.cols)
+        if dA is not None:
+            g = dA.contiguous() if g is None else g + dA
+        fwd, perm, long_rows = _softmax_side(dyn, "row")
+        n_long = 0 if long_rows is None else long_rows.numel()
+        ds = torch.empty_like(alpha)
+        _lib.check(_lib.load().mmrec_segment_softmax_bwd_f32(_p(fwd.rowptr), fwd.n_rows, _p(perm), _p(long_rows), n_long,
+                                                             _p(alpha), _p(g), alpha.numel(), _p(ds), _stream()),
+                   "segment_softmax_bwd")
+        dQ = dKV = None
+        if want_q:                                              # d s_e reaches Q[row_e] ...
+            dQ = _spmm_with(dyn.fwd, ds[dyn.perm].contiguous(), KV)
+        if want_kv:                                             # ... and KV[col_e], which the weighted sum reads as well
+            dKV = _spmm_with(dyn.bwd, ds[dyn.perm_t].contiguous(), Q)
+            if dY is not None:
+                dKV = _spmm_with(dyn.bwd, alpha[dyn.perm_t].contiguous(), dY) + dKV
+        if same:
+            return dQ + dKV, None, None, None
+        return dQ, dKV, None, None
+
+
+def edge_attention(Q, KV, dyn, eps=1e-16):
+    """Attention over the edges of `dyn` ("GAT aggregation"): for every edge e = (row, col) the score s_e = <Q[row], KV[col]>,
+    alpha = the softmax of the scores over the edges that share a row (eps in the denominator), Y[row] = sum_e alpha_e KV[col];
+    -> (Y [n_rows, 64], alpha [n_edges] in the order of dyn's edge list).  GRCN's content GCN (grcn.py:63-72).
+    Served by the kernel (`edge_attention_served`): ONE launch (+ one for the rows longer than `edge_attention_group_max()`)
+    that gathers every KV[col] once for both the score and the sum, instead of `edge_dot` -> `edge_softmax` -> `spmm_vals`,
+    which gather it twice and write and re-read the scores and the weights; no atomics, so Y and alpha repeat bit for bit.  A
+    row that holds a NaN, a +inf or nothing but -inf among its scores is NaN in its alphas and in Y.  Backward, from the saved
+    Q, KV and alpha (no [n_edges] score is kept), composed of the existing kernels: g = <dY[row], KV[col]> per edge (+ the
+    gradient arriving at alpha), ds = the segment softmax's backward, dQ = SpMM(dyn.fwd, ds) KV, dKV = SpMM(dyn.bwd, alpha) dY +
+    SpMM(dyn.bwd, ds) Q; `Q is KV`: the two are summed.  The long-row list is built on the host at the first call on a DynGraph:
+    call once before capturing a step.
+    EVERY OTHER CASE (CPU tensors, other widths or dtypes, non-contiguous tables, table lengths that are not dyn's, the switch
+    off) is exactly `edge_dot` -> `edge_softmax` -> `spmm_vals` with stock autograd."""
+    if edge_attention_served(Q, KV, dyn):
+        return _EdgeAttention.apply(Q, None if Q is KV else KV, dyn, float(eps))
+    alpha = edge_softmax(edge_dot(Q, KV, dyn.rows, dyn.cols, dyn=dyn), dyn, eps=eps)
+    return spmm_vals(dyn, KV, alpha), alpha
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

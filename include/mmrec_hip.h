@@ -121,6 +121,34 @@ int mmrec_spmm_csr_f32_layergcn(const int32_t* rowptr, const int32_t* colidx, co
                                 float* acc_out, int32_t n_rows, int32_t d, int32_t long_row_threshold,
                                 const int32_t* long_rows, const int32_t* long_chunk_ptr, int32_t n_long,
                                 int32_t n_chunks, float* partials, int32_t* long_tickets, mmrec_stream_t stream);
+/* Row schedule of a large graph (additive to ABI 16).  mmrec_spmm_csr_sched_f32 is mmrec_spmm_csr_f32 with the row blocks
+ * visiting the SHORT rows (nnz <= long_row_threshold, empty rows included) in the order of a caller-built schedule instead of
+ * row-id order: slot i visits row sched_row[i], whose (column, value) entries are sched_col / sched_val[sched_span[2 i] ..
+ * sched_span[2 i + 1]) -- a packed copy of the row's CSR segment, entries in CSR order.  sched_row must list every short row
+ * exactly once and no long row (n_short of them); long rows are served from the CSR by the chunk blocks as before.  d = 64 k
+ * only (k <= 6; the feature slices keep mmrec_spmm_csr_f32).  Every row's sum runs over the same entries in the same order:
+ * the results are BIT-IDENTICAL to mmrec_spmm_csr_f32 for any valid schedule; only the order in which rows meet in the
+ * caches changes (rows that share a cold column side by side: that column is fetched past L2 once per block, not once per
+ * row).  mmrec_spmm_csr_sched_f32_layergcn is the same twin of mmrec_spmm_csr_f32_layergcn.
+ * mmrec_spmm_row_keys writes, for every row, the sort key such a schedule is built from: key[row] = among the row's columns
+ * with col_degree <= key_deg_max the one with the largest col_degree (first in row order among equals), key_degree[row] =
+ * that degree; -1 and 0 for a row without such a column, an empty row, or a long row.  col_degree: int32 [n_cols]. */
+int mmrec_spmm_csr_sched_f32(const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* X, float* Y,
+                             const float* Z, const float* acc_in, float* acc_out, int32_t n_rows, int32_t d, float alpha,
+                             float beta, float acc_scale, int32_t long_row_threshold, const int32_t* long_rows,
+                             const int32_t* long_chunk_ptr, int32_t n_long, int32_t n_chunks, float* partials,
+                             int32_t* long_tickets, const int32_t* sched_row, const int32_t* sched_span,
+                             const int32_t* sched_col, const float* sched_val, int32_t n_short, mmrec_stream_t stream);
+int mmrec_spmm_csr_sched_f32_layergcn(const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* X,
+                                      float* Y, const float* ego, float* scaled, float* w, const float* acc_in,
+                                      float* acc_out, int32_t n_rows, int32_t d, int32_t long_row_threshold,
+                                      const int32_t* long_rows, const int32_t* long_chunk_ptr, int32_t n_long,
+                                      int32_t n_chunks, float* partials, int32_t* long_tickets, const int32_t* sched_row,
+                                      const int32_t* sched_span, const int32_t* sched_col, const float* sched_val,
+                                      int32_t n_short, mmrec_stream_t stream);
+int mmrec_spmm_row_keys(const int32_t* rowptr, const int32_t* colidx, const int32_t* col_degree, int32_t n_rows,
+                        int32_t long_row_threshold, int32_t key_deg_max, int32_t* key, int32_t* key_degree,
+                        mmrec_stream_t stream);
 /* Host-side plan helpers (pure CPU, rowptr is a HOST pointer).  count: returns n_long and n_chunks;
  * fill: writes long_rows[n_long] and long_chunk_ptr[n_long+1] (host arrays the caller copies to the
  * device).  partials workspace = n_chunks * d * 4 bytes (d: the row width of the SpMM call). */

@@ -28,6 +28,12 @@ SIGNATURES = {
                                      c_float, c_float, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P]),
     "mmrec_spmm_csr_f32_layergcn": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32,
                                               _P, _P, c_int32, c_int32, _P, _P, _P]),
+    "mmrec_spmm_csr_sched_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_float,
+                                           c_float, c_float, c_int32, _P, _P, c_int32, c_int32, _P, _P,
+                                           _P, _P, _P, _P, c_int32, _P]),
+    "mmrec_spmm_csr_sched_f32_layergcn": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32,
+                                                    _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P]),
+    "mmrec_spmm_row_keys": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P]),
     "mmrec_spmm_plan_count": (c_int32, [_P, c_int32, c_int32, _P, _P]),
     "mmrec_spmm_plan_fill": (c_int32, [_P, c_int32, c_int32, _P, _P]),
     "mmrec_cos_scale_fwd_f32": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, _P]),

@@ -64,6 +64,19 @@ struct RowEpilogue {
     float* w_out;
 };
 
+// The row schedule of a large graph (hip_ops.CsrGraph): the short rows in VISITING order -- rows that gather the
+// same cold column sit in the same row block, so that column is fetched past L2 once per block and not once per row -- with
+// their (col, val) entries packed in that order, so the index stream stays one coalesced read (visiting rows out of id order
+// through rowptr / colidx costs a whole 128-B line per row and stream: more than the gathers saved).  A row's entries keep
+// their CSR order: the same sums, bit for bit.
+struct RowSchedule {
+    const int32_t* row;   // [n_short] the row visited at a slot
+    const int2* span;     // [n_short] its [begin, end) in col / val
+    const int32_t* col;   // the short rows' column ids, slot after slot
+    const float* val;
+    int n_short;
+};
+
 // LG: the LayerGCN epilogue, its own instantiation -- compiled into the common kernel its registers cost every launch occupancy
 template <int DCH, bool LG>
 __device__ __forceinline__ void store_row(const RowEpilogue& ep, int row, int lane16, const float4 (&sum)[DCH]) {
@@ -171,13 +184,15 @@ __device__ __forceinline__ void reduce_long_row(const float* __restrict__ partia
 // first: they are the longest dependency chains), blocks [n_chunks, ...) process 64 short rows each.
 // (Other block orders -- chunk blocks interleaved with row blocks, user rows mixed with item rows -- give the same bits and
 // lose at config 5: profiles/r07_spmm_block_order_rejected.patch, r07_spmm_phases.log.)
-template <int DCH, bool LG>
+// SCHED: the row blocks walk a RowSchedule (short rows only, no long-row test) instead of 64 consecutive row ids; the chunk
+// blocks are the same code on the same CSR.  Its own instantiation: the identity form compiles to what it was without it.
+template <int DCH, bool LG, bool SCHED>
 __global__ __launch_bounds__(256) void spmm_rows_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
     const float* __restrict__ vals, const float* __restrict__ X, RowEpilogue ep, int n_rows,
     int long_t, int rows_per_group, const int32_t* __restrict__ long_rows,
     const int32_t* __restrict__ long_chunk_ptr, int n_long, int n_chunks,
-    float* __restrict__ partials, int32_t* __restrict__ tickets) {
+    float* __restrict__ partials, int32_t* __restrict__ tickets, RowSchedule sched) {
     __shared__ float4 red[16][16 * DCH];
     __shared__ int s_last;
     const int lane16 = threadIdx.x & 15;
@@ -246,6 +261,22 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(
         if (threadIdx.x == 0) __hip_atomic_store(tickets + lo, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
+    if (SCHED) {
+        const int slot0 = ((int)blockIdx.x - n_chunks) * 16 * rows_per_group + g;
+#pragma unroll 1
+        for (int i = 0; i < rows_per_group; ++i) {
+            const int slot = slot0 + i * 16;
+            if (slot >= sched.n_short) break;
+            const int row = sched.row[slot];
+            const int2 se = sched.span[slot];
+            float4 acc[DCH];
+#pragma unroll
+            for (int ch = 0; ch < DCH; ++ch) acc[ch] = f4_zero();
+            gather_span<DCH>(sched.col, sched.val, X4, se.x, se.y, lane16, acc);
+            store_row<DCH, LG>(ep, row, lane16, acc);
+        }
+        return;
+    }
     const int row0 = ((int)blockIdx.x - n_chunks) * 16 * rows_per_group + g;
 #pragma unroll 1
     for (int i = 0; i < rows_per_group; ++i) {
@@ -273,13 +304,15 @@ __global__ __launch_bounds__(256) void spmm_long_reduce_kernel(
     reduce_long_row<DCH, false, LG>(partials, c0, c1, long_rows[i], ep, red);
 }
 
-template <int DCH, bool LG = false>
+template <int DCH, bool LG = false, bool SCHED = false>
 void launch_spmm(hipStream_t s, int blocks, int nch, const int32_t* rowptr, const int32_t* colidx,
                  const float* vals, const float* X, const RowEpilogue& ep, int n_rows, int long_t,
                  int rows_per_group, const int32_t* long_rows, const int32_t* long_chunk_ptr, int n_long,
-                 float* partials, int32_t* tickets) {
-    hipLaunchKernelGGL((spmm_rows_kernel<DCH, LG>), dim3(blocks + nch), dim3(256), 0, s, rowptr, colidx, vals, X,
-                       ep, n_rows, long_t, rows_per_group, long_rows, long_chunk_ptr, n_long, nch, partials, tickets);
+                 float* partials, int32_t* tickets, const RowSchedule& sched = RowSchedule{}) {
+    if (blocks + nch > 0)
+        hipLaunchKernelGGL((spmm_rows_kernel<DCH, LG, SCHED>), dim3(blocks + nch), dim3(256), 0, s, rowptr, colidx, vals, X,
+                           ep, n_rows, long_t, rows_per_group, long_rows, long_chunk_ptr, n_long, nch, partials, tickets,
+                           sched);
     if (!tickets && n_long > 0 && nch > n_long)  // at least one row spans several chunks
         hipLaunchKernelGGL((spmm_long_reduce_kernel<DCH, LG>), dim3(n_long), dim3(256), 0, s, long_rows,
                            long_chunk_ptr, n_long, partials, ep);
@@ -334,6 +367,45 @@ __global__ __launch_bounds__(256) void cos_scale_bwd_kernel(
     dg = f4_fma(dw * inv, e, dg);
     dg = f4_fma(-dw * cg, g, dg);
     reinterpret_cast<float4*>(dEgo)[off] = dg;
+}
+
+// Plan-time half of the row schedule: the KEY of every short row -- among the row's columns of column degree <= deg_max (the
+// cold ones: L2 keeps the popular columns anyway) the one with the LARGEST degree (the most rows to share it with), the first
+// in row order among equals; -1 / degree 0 when the row has none (or is long, or empty).  One 16-lane group per row, one
+// coalesced read of the column ids.
+__global__ __launch_bounds__(256) void spmm_row_keys_kernel(const int32_t* __restrict__ rowptr,
+                                                            const int32_t* __restrict__ colidx,
+                                                            const int32_t* __restrict__ col_degree, int n_rows, int long_t,
+                                                            int deg_max, int32_t* __restrict__ key,
+                                                            int32_t* __restrict__ key_degree) {
+    const int lane16 = threadIdx.x & 15;
+    const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (row >= n_rows) return;  // uniform for the group
+    const int s = rowptr[row], e = rowptr[row + 1];
+    int bd = 0, bp = INT32_MAX, bc = -1;
+    if (e - s <= long_t)
+        for (int k = s + lane16; k < e; k += 16) {  // ascending positions: `>` keeps the lane's first
+            const int c = colidx[k];
+            const int dg = col_degree[c];
+            if (dg <= deg_max && dg > bd) {
+                bd = dg;
+                bp = k;
+                bc = c;
+            }
+        }
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) {
+        const int od = __shfl_xor(bd, m, 16), op = __shfl_xor(bp, m, 16), oc = __shfl_xor(bc, m, 16);
+        if (od > bd || (od == bd && op < bp)) {
+            bd = od;
+            bp = op;
+            bc = oc;
+        }
+    }
+    if (lane16 == 0) {
+        key[row] = bc;
+        key_degree[row] = bd;
+    }
 }
 
 }  // namespace
@@ -438,6 +510,92 @@ extern "C" int mmrec_spmm_csr_f32_layergcn(const int32_t* rowptr, const int32_t*
     int32_t* tickets = n_long > 0 ? long_tickets : nullptr;
     launch_spmm<1, true>(s, blocks, nch, rowptr, colidx, vals, X, ep, n_rows, long_t, rows_per_group, long_rows,
                          long_chunk_ptr, n_long, partials, tickets);
+    MMREC_RETURN_LAUNCH_STATUS();
+}
+
+// The scheduled forms (additive to ABI 16): the row blocks walk the graph's RowSchedule, the chunk blocks the CSR.
+namespace {
+bool sched_args_ok(const int32_t* sched_row, const int32_t* sched_span, const int32_t* sched_col, const float* sched_val,
+                   int32_t n_short, int32_t n_rows) {
+    if (n_short < 0 || n_short > n_rows) return false;
+    return n_short == 0 || (sched_row && sched_span && sched_col && sched_val);
+}
+}  // namespace
+
+extern "C" int mmrec_spmm_csr_sched_f32(const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                                        const float* X, float* Y, const float* Z, const float* acc_in,
+                                        float* acc_out, int32_t n_rows, int32_t d, float alpha, float beta,
+                                        float acc_scale, int32_t long_row_threshold,
+                                        const int32_t* long_rows, const int32_t* long_chunk_ptr,
+                                        int32_t n_long, int32_t n_chunks, float* partials, int32_t* long_tickets,
+                                        const int32_t* sched_row, const int32_t* sched_span, const int32_t* sched_col,
+                                        const float* sched_val, int32_t n_short, mmrec_stream_t stream) {
+    if (d <= 0 || d % MMREC_EMB_DIM || d / MMREC_EMB_DIM > 6) return MMREC_ERR_UNSUPPORTED;
+    if (n_rows < 0 || n_long < 0 || n_chunks < 0 || long_row_threshold < 0) return MMREC_ERR_BAD_ARG;
+    if (n_rows == 0) return 0;
+    if (!rowptr || !X || (!Y && !acc_out)) return MMREC_ERR_BAD_ARG;
+    if (acc_out && !acc_in) return MMREC_ERR_BAD_ARG;
+    if (n_long > 0 && (!long_rows || !long_chunk_ptr || !partials || n_chunks <= 0))
+        return MMREC_ERR_BAD_ARG;
+    if (!sched_args_ok(sched_row, sched_span, sched_col, sched_val, n_short, n_rows)) return MMREC_ERR_BAD_ARG;
+    if (Y == X || acc_out == X) return MMREC_ERR_BAD_ARG;  // other rows still gather from X
+    RowEpilogue ep{Z, Y, acc_in, acc_out, alpha, Z ? beta : 0.f, acc_scale, nullptr, nullptr, nullptr};
+    const RowSchedule sched{sched_row, reinterpret_cast<const int2*>(sched_span), sched_col, sched_val, n_short};
+    hipStream_t s = mmrec_stream(stream);
+    const int rows_per_group = MMREC_SPMM_RPG(n_rows);
+    const int blocks = (n_short + 16 * rows_per_group - 1) / (16 * rows_per_group);  // long rows are not in the schedule
+    const int long_t = n_long > 0 ? long_row_threshold : INT32_MAX;
+    const int nch = n_long > 0 ? n_chunks : 0;
+    int32_t* tickets = n_long > 0 ? long_tickets : nullptr;
+#define MMREC_SPMM_CASE(D)                                                                                      \
+    case D:                                                                                                     \
+        launch_spmm<D, false, true>(s, blocks, nch, rowptr, colidx, vals, X, ep, n_rows, long_t, rows_per_group, \
+                                    long_rows, long_chunk_ptr, n_long, partials, tickets, sched);               \
+        break;
+    switch (d / MMREC_EMB_DIM) {
+        MMREC_SPMM_CASE(1) MMREC_SPMM_CASE(2) MMREC_SPMM_CASE(3) MMREC_SPMM_CASE(4) MMREC_SPMM_CASE(5)
+        MMREC_SPMM_CASE(6)
+    }
+#undef MMREC_SPMM_CASE
+    MMREC_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int mmrec_spmm_csr_sched_f32_layergcn(const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                                                 const float* X, float* Y, const float* ego, float* scaled, float* w,
+                                                 const float* acc_in, float* acc_out, int32_t n_rows, int32_t d,
+                                                 int32_t long_row_threshold, const int32_t* long_rows,
+                                                 const int32_t* long_chunk_ptr, int32_t n_long, int32_t n_chunks,
+                                                 float* partials, int32_t* long_tickets, const int32_t* sched_row,
+                                                 const int32_t* sched_span, const int32_t* sched_col,
+                                                 const float* sched_val, int32_t n_short, mmrec_stream_t stream) {
+    if (d != MMREC_EMB_DIM) return MMREC_ERR_UNSUPPORTED;
+    if (n_rows < 0 || n_long < 0 || n_chunks < 0 || long_row_threshold < 0) return MMREC_ERR_BAD_ARG;
+    if (n_rows == 0) return 0;
+    if (!rowptr || !X || !ego || !scaled || !w) return MMREC_ERR_BAD_ARG;
+    if (n_long > 0 && (!long_rows || !long_chunk_ptr || !partials || n_chunks <= 0)) return MMREC_ERR_BAD_ARG;
+    if (!sched_args_ok(sched_row, sched_span, sched_col, sched_val, n_short, n_rows)) return MMREC_ERR_BAD_ARG;
+    if (Y == X || scaled == X || acc_out == X) return MMREC_ERR_BAD_ARG;  // other rows still gather from X
+    RowEpilogue ep{nullptr, Y, acc_in, acc_out, 1.f, 0.f, 1.f, ego, scaled, w};
+    const RowSchedule sched{sched_row, reinterpret_cast<const int2*>(sched_span), sched_col, sched_val, n_short};
+    hipStream_t s = mmrec_stream(stream);
+    const int rows_per_group = MMREC_SPMM_RPG(n_rows);
+    const int blocks = (n_short + 16 * rows_per_group - 1) / (16 * rows_per_group);
+    const int long_t = n_long > 0 ? long_row_threshold : INT32_MAX;
+    const int nch = n_long > 0 ? n_chunks : 0;
+    int32_t* tickets = n_long > 0 ? long_tickets : nullptr;
+    launch_spmm<1, true, true>(s, blocks, nch, rowptr, colidx, vals, X, ep, n_rows, long_t, rows_per_group, long_rows,
+                               long_chunk_ptr, n_long, partials, tickets, sched);
+    MMREC_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int mmrec_spmm_row_keys(const int32_t* rowptr, const int32_t* colidx, const int32_t* col_degree,
+                                   int32_t n_rows, int32_t long_row_threshold, int32_t key_deg_max, int32_t* key,
+                                   int32_t* key_degree, mmrec_stream_t stream) {
+    if (n_rows < 0 || long_row_threshold < 0 || key_deg_max < 0) return MMREC_ERR_BAD_ARG;
+    if (n_rows == 0) return 0;
+    if (!rowptr || !colidx || !col_degree || !key || !key_degree) return MMREC_ERR_BAD_ARG;
+    hipLaunchKernelGGL(spmm_row_keys_kernel, dim3((n_rows + 15) / 16), dim3(256), 0, mmrec_stream(stream), rowptr, colidx,
+                       col_degree, n_rows, long_row_threshold, key_deg_max, key, key_degree);
     MMREC_RETURN_LAUNCH_STATUS();
 }
 

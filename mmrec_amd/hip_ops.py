@@ -41,6 +41,19 @@ def default_long_row_threshold(n_cols):
         return int(forced)
     return 16 if n_cols <= (1 << 18) else 32
 
+
+ROW_SCHEDULE_MIN_COLS = 1 << 18    # graphs with more columns get a row schedule (CsrGraph(row_schedule=None))
+SPMM_KEY_DEG_MAX = 128             # MMREC_SPMM_KEY_DEG_MAX: a column gathered by more rows than this is never a row's key
+
+
+def spmm_key_deg_max():
+    """The largest column degree a row-schedule key may have.  Measured flat over 64 / 128 / 256 (tools/prof_spmm_row_order.py
+    --key-deg-max); the environment override is a measurement aid like MMREC_LONG_ROW_THRESHOLD."""
+    import os
+    forced = os.environ.get("MMREC_SPMM_KEY_DEG_MAX")
+    return int(forced) if forced else SPMM_KEY_DEG_MAX
+
+
 TOPK_MAX = 128            # MMREC_TOPK_MAX: row widths that are a multiple of 32 with <= 2,097,152 candidates; 64 for every other shape (the library says so: MMREC_ERR_UNSUPPORTED)
 BPR_LOGSIG, BPR_GAMMA = 0, 1
 
@@ -110,10 +123,19 @@ class CsrGraph:
 
     `symmetric=True` (structure and values; all D^-1/2 A D^-1/2 graphs) lets the
     backward reuse the same CSR; otherwise `transpose()` builds A^T once (graphs are frozen or
-    rebuilt once per epoch)."""
+    rebuilt once per epoch).
+
+    `row_schedule` (None: graphs with more than ROW_SCHEDULE_MIN_COLS columns -- a function of the column count, like the
+    long-row threshold, so a graph and its row blocks decide alike; True / False: forced): the plan also holds a VISITING ORDER
+    of the short rows in which rows that gather the same cold column are neighbours, with a packed copy of
+    those rows' (column, value) entries in that order, and the 64 k-wide launches walk it.  Results are bit-identical to the
+    identity order (each row sums the same entries in the same order).  It costs device memory: 8 B per short nonzero + 12 B
+    per short row ON TOP of the CSR (about 131 MB at config 5: 14.2M short nonzeros, 1.46M short rows) and one plan-time
+    pass (a key kernel, one sort, one gather).  The copy holds `vals` as they were at construction: a caller that swaps
+    `g.vals` afterwards (spmm_vals, the DynGraph forms) is served by the identity path."""
 
     def __init__(self, rowptr, colidx, vals, n_rows, n_cols, symmetric=False,
-                 long_row_threshold=LONG_ROW_DEFAULT, rowptr_host=None):
+                 long_row_threshold=LONG_ROW_DEFAULT, rowptr_host=None, row_schedule=None):
         self.rowptr = _chk(rowptr, torch.int32, "rowptr", 1)
         self.colidx = _chk(colidx, torch.int32, "colidx", 1)
         self.vals = _chk(vals, torch.float32, "vals", 1)
@@ -123,6 +145,7 @@ class CsrGraph:
         self.long_row_threshold = int(default_long_row_threshold(self.n_cols) if long_row_threshold is None
                                       else long_row_threshold)
         self._t = self if symmetric else None
+        self.row_schedule = bool(self.n_cols > ROW_SCHEDULE_MIN_COLS if row_schedule is None else row_schedule)
         self._plan(rowptr_host)
 
     # -- plan: rows longer than the threshold are cut into fixed-size chunks (host side, C helper)
@@ -154,6 +177,65 @@ class CsrGraph:
             self.long_rows = self.long_chunk_ptr = self.long_tickets = None
             self.max_row_chunks = 1
         self._partials = {}
+        self.sched = None
+        if self.row_schedule:
+            self._plan_schedule()
+
+    def _plan_schedule(self):
+        """The visiting order of the short rows and their packed index stream (device work: one key kernel, torch sorts).
+
+        key(row) = among the row's columns gathered by at most spmm_key_deg_max() rows the one gathered by the MOST rows (the
+        first in row order among equals): L2 keeps the popular columns whatever the order, a cold one is fetched once per row
+        that gathers it unless those rows run together.  Order: stable sort of the short rows by (band, key degree
+        descending, key, row id), rows without a key last in their band -- the rows of one key fill consecutive slots, so one
+        or two row blocks, and the big groups come first.  Band 0: rows whose reference column (the key; for a row without
+        one its first column) has a LARGER id than the row; band 1: everything else (empty rows too).  On a [users; items]
+        bipartite layout that is all user rows before all item rows, the phase order the identity launch has
+        (profiles/r07_spmm_phases.log: mixing the two costs 2-25 %); on other graphs it is merely a fixed rule."""
+        lib = _lib.load()
+        dev, n = self.rowptr.device, self.n_rows
+        deg = (self.rowptr[1:] - self.rowptr[:-1])
+        short = torch.nonzero(deg <= self.long_row_threshold).squeeze(1)               # ascending row ids (int64)
+        key = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        kdeg = torch.zeros(n, dtype=torch.int32, device=dev)
+        if self.nnz > 0 and n > 0:
+            if self.symmetric and self.n_cols == n:
+                coldeg = deg.contiguous()
+            else:
+                coldeg = torch.bincount(self.colidx, minlength=self.n_cols).to(torch.int32)
+            _lib.check(lib.mmrec_spmm_row_keys(_p(self.rowptr), _p(self.colidx), _p(coldeg), n, self.long_row_threshold,
+                                               spmm_key_deg_max(), _p(key), _p(kdeg), _stream()), "spmm_row_keys")
+        self.row_key, self.row_key_degree = key, kdeg          # the hook for other keys (community labels): a follow-up
+        k, kd, dg = key[short].long(), kdeg[short].long(), deg[short].long()
+        first = self.colidx[self.rowptr[:-1][short].long().clamp_(max=max(self.nnz - 1, 0))].long() if self.nnz > 0 else k
+        ref = torch.where(k >= 0, k, torch.where(dg > 0, first, torch.full_like(k, -1)))
+        band = (ref <= short).long()
+        # one 63-bit composite: band | 2^31 - 1 - key degree (no key: degree 0, last) | key ; the stable sort keeps row ids ascending
+        comp = (band << 62) | (((1 << 31) - 1 - kd) << 31) | k.clamp(min=0)
+        order = torch.sort(comp, stable=True)[1]
+        rows = short[order]
+        lens = dg[order]
+        end = torch.cumsum(lens, 0)
+        begin = end - lens
+        total = int(end[-1].item()) if rows.numel() else 0
+        src0 = self.rowptr[:-1].long()[rows]
+        pos = torch.arange(total, dtype=torch.int64, device=dev) + torch.repeat_interleave(src0 - begin, lens, output_size=total)
+        self.sched = {
+            "row": rows.to(torch.int32).contiguous(),
+            "span": torch.stack([begin, end], 1).to(torch.int32).contiguous(),
+            "col": self.colidx.index_select(0, pos) if total else torch.zeros(1, dtype=torch.int32, device=dev),
+            "val": self.vals.index_select(0, pos) if total else torch.zeros(1, dtype=torch.float32, device=dev),
+            "n_short": int(rows.numel()),
+            "vals_of": self.vals,       # the values the copy was packed from (see scheduled())
+        }
+
+    def scheduled(self, d):
+        """the schedule, if this launch may use it: 64 k-wide rows, and `vals` still the tensor the schedule packed"""
+        sc = self.sched
+        return sc if sc is not None and d % EMB_DIM == 0 and sc["vals_of"] is self.vals else None
+
+    def schedule_bytes(self):
+        return 0 if self.sched is None else sum(self.sched[k].numel() * self.sched[k].element_size() for k in ("row", "span", "col", "val"))
 
     def checked(self, rc, what):
         """_lib.check for a launch that uses the last-arriver tickets: they are left at zero by every COMPLETED launch; after a
@@ -228,7 +310,7 @@ class CsrGraph:
         dev = self.rowptr.device
         return CsrGraph(torch.from_numpy(rph).to(dev), self.colidx[s:e].contiguous(),
                         self.vals[s:e].contiguous(), r1 - r0, self.n_cols,
-                        long_row_threshold=self.long_row_threshold, rowptr_host=rph)
+                        long_row_threshold=self.long_row_threshold, rowptr_host=rph, row_schedule=self.row_schedule)
 
 
 def _mode_labels(rows, lab_c, n_rows, n_labels):
@@ -357,6 +439,15 @@ def spmm_raw(g: CsrGraph, X, Y=None, Z=None, acc_in=None, acc_out=None, alpha=1.
             _chk(t, torch.float32, nm, 2)
             if t.shape[0] < g.n_rows or t.shape[1] != d:
                 raise _lib.MMRecHipError("%s must be [>=%d, %d]" % (nm, g.n_rows, d))
+    sc = g.scheduled(d)
+    if sc is not None:      # large graph: the row blocks visit the short rows in the plan's order (same bits)
+        g.checked(lib.mmrec_spmm_csr_sched_f32(_p(g.rowptr), _p(g.colidx), _p(g.vals), _p(X), _p(Y), _p(Z),
+                                               _p(acc_in), _p(acc_out), g.n_rows, d, float(alpha),
+                                               float(beta), float(acc_scale), g.long_row_threshold,
+                                               _p(g.long_rows), _p(g.long_chunk_ptr), g.n_long, g.n_chunks,
+                                               _p(g.partials_for(d)), _p(g.long_tickets), _p(sc["row"]), _p(sc["span"]),
+                                               _p(sc["col"]), _p(sc["val"]), sc["n_short"], _stream()), "spmm_csr_sched_f32")
+        return Y if Y is not None else acc_out
     g.checked(lib.mmrec_spmm_csr_f32(_p(g.rowptr), _p(g.colidx), _p(g.vals), _p(X), _p(Y), _p(Z),
                                      _p(acc_in), _p(acc_out), g.n_rows, d, float(alpha),
                                      float(beta), float(acc_scale), g.long_row_threshold,
@@ -711,11 +802,15 @@ class _LayerGCNSum(torch.autograd.Function):
         for layer in range(L):                    # SpMM + cosine re-weighting + layer sum: ONE launch per layer
             y = torch.empty_like(E0) if need_y else None
             out, w = torch.empty_like(E0), torch.empty(n, dtype=torch.float32, device=E0.device)
-            g.checked(lib.mmrec_spmm_csr_f32_layergcn(
-                _p(g.rowptr), _p(g.colidx), _p(g.vals), _p(cur), _p(y), _p(E0), _p(out), _p(w),
-                _p(acc) if layer > 0 else None, _p(acc), g.n_rows, EMB_DIM, g.long_row_threshold, _p(g.long_rows),
-                _p(g.long_chunk_ptr), g.n_long, g.n_chunks, _p(g.partials_for(EMB_DIM)), _p(g.long_tickets), _stream()),
-                "spmm_layergcn")
+            args = (_p(g.rowptr), _p(g.colidx), _p(g.vals), _p(cur), _p(y), _p(E0), _p(out), _p(w),
+                    _p(acc) if layer > 0 else None, _p(acc), g.n_rows, EMB_DIM, g.long_row_threshold, _p(g.long_rows),
+                    _p(g.long_chunk_ptr), g.n_long, g.n_chunks, _p(g.partials_for(EMB_DIM)), _p(g.long_tickets))
+            sc = g.scheduled(EMB_DIM)
+            if sc is not None:
+                g.checked(lib.mmrec_spmm_csr_sched_f32_layergcn(*args, _p(sc["row"]), _p(sc["span"]), _p(sc["col"]), _p(sc["val"]),
+                                                                sc["n_short"], _stream()), "spmm_sched_layergcn")
+            else:
+                g.checked(lib.mmrec_spmm_csr_f32_layergcn(*args, _stream()), "spmm_layergcn")
             ys.append(y), ws.append(w)
             cur = out
         ctx.g, ctx.L = g, L
@@ -1764,7 +1859,7 @@ class DynGraph:
             rowptr = torch.zeros(nr + 1, dtype=torch.int64, device=dev)
             rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=nr), 0)
             g = CsrGraph(rowptr.to(torch.int32), c[perm].to(torch.int32).contiguous(), zeros, nr, nc,
-                         long_row_threshold=long_row_threshold)
+                         long_row_threshold=long_row_threshold, row_schedule=False)   # the values change every call
             return g, perm
         self.fwd, self.perm = build(rows, cols, self.n_rows, self.n_cols)
         self.bwd, self.perm_t = build(cols, rows, self.n_cols, self.n_rows)

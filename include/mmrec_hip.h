@@ -450,6 +450,42 @@ int mmrec_edge_attention_f32(const int32_t* rowptr, int32_t n_rows, const int32_
                              int64_t n_kv, int32_t d, int64_t n_edges, float eps, float* Y, float* alpha,
                              mmrec_stream_t stream);
 
+/* Backward of mmrec_edge_attention_f32 from its results alpha and Y, every row gathered once.  ADDITIVE to ABI 16: one new
+ * symbol, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: autograd through grcn.py:63-72, and the composition mmrec_edge_dot_f32 -> mmrec_segment_softmax_bwd_f32 -> three
+ *           mmrec_spmm_csr_f32 with permuted copies of ds and alpha.
+ * With row r, slot j at position p, column c = colidx[j] as in the forward:
+ *   g_p    = <dY[r], KV[c]> + dAlpha[p]                         dY [n_rows, 64] and dAlpha [n_edges]: one may be NULL, not both
+ *   t_r    = <dY[r], Y[r]> + sum_p alpha_p dAlpha[p]            (= sum_p alpha_p g_p: Y is the forward's, needed only with dY)
+ *   ds_p   = alpha_p (g_p - t_r)                                ds [n_edges], caller-owned, ALWAYS written, the caller's order
+ *   dQ[r]  = sum_p ds_p KV[c]                                   dQ [n_rows, 64]
+ *   dKV[c] = dKV_base[c] + sum over the edges of column c of (alpha_p dY[r] + ds_p Q[r])         dKV, dKV_base [n_kv, 64]
+ * the exact derivative of the forward as written (maximum detached, eps in the denominator).  dQ or dKV may be NULL, not both.
+ * dKV_base may be NULL and may be dQ (Q == KV: dKV is then the whole gradient); it must not be dKV.  Outputs must not alias
+ * inputs.  Row pass (ds, dQ): the forward's CSR, perm, long_rows / n_long and access shape; a listed row's 16 partial sums are
+ * added in a fixed order.  Column pass (dKV; its arguments and Q are unused when dKV == NULL): the transposed CSR of the same
+ * edge list -- rowptr_t [n_kv + 1], rowidx_t [n_edges] (the row of each slot), perm_t (NULL = identity), and long_cols
+ * [n_long_t], the columns with more than mmrec_edge_attention_group_max() entries listed as long_rows is; it reads alpha and
+ * ds through perm_t.  n_long == 0 / n_long_t == 0: the 16-lane groups serve every row / column.
+ * EVERY row of dQ and of dKV is written.  An absent edge -- a column id outside [0, n_kv), a row id outside [0, n_rows) on the
+ * transposed side, a position outside [0, n_edges) -- is never an address and adds nothing; where its position is valid its
+ * ds is written as 0.  The two sides must name the SAME edges: the forward leaves alpha undefined at the position of an edge
+ * that is absent on the row side, and the column pass decides presence from rowidx_t and perm_t alone, so a transposed CSR
+ * that still lists such an edge reads that undefined alpha -- dKV is then undefined.  No atomics: the bits of ds, dQ and
+ * dKV are a function of the inputs and the row and column lengths.  A row whose alpha is NaN is NaN in its ds, in dQ[r] and
+ * in the dKV rows of its own columns, and nowhere else.  A hub is one workgroup in each pass, as in the forward.
+ * d != 64: MMREC_ERR_UNSUPPORTED; negative sizes: MMREC_ERR_BAD_ARG; n_rows == 0 or n_edges == 0: 0 and no launch (pointers
+ * may be NULL; nothing is written: the caller's zeros); n_edges or n_kv > 2^31 - 1: MMREC_ERR_UNSUPPORTED; n_q < n_rows, a NULL
+ * rowptr / colidx / KV / alpha / ds, dY and dAlpha both NULL, dY without Y, dQ and dKV both NULL, dKV with a NULL rowptr_t /
+ * rowidx_t / Q or with dKV_base == dKV, a long count > 0 with a NULL list: MMREC_ERR_BAD_ARG -- in this order, before any
+ * launch.  No synchronisation, no allocation, capture-safe, no global state. */
+int mmrec_edge_attention_bwd_f32(const int32_t* rowptr, int32_t n_rows, const int32_t* colidx, const int64_t* perm,
+                                 const int32_t* long_rows, int32_t n_long, const int32_t* rowptr_t, const int32_t* rowidx_t,
+                                 const int64_t* perm_t, const int32_t* long_cols, int32_t n_long_t, const float* Q, int64_t n_q,
+                                 const float* KV, int64_t n_kv, const float* Y, const float* alpha, const float* dY,
+                                 const float* dAlpha, int32_t d, int64_t n_edges, float* ds, float* dQ, float* dKV,
+                                 const float* dKV_base, mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

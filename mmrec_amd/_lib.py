@@ -71,6 +71,8 @@ SIGNATURES = {
     "mmrec_edge_attention_group_max": (c_int32, []),
     "mmrec_edge_attention_f32": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, _P, c_int64, _P, c_int64, c_int32, c_int64, c_float,
                                            _P, _P, _P]),
+    "mmrec_edge_attention_bwd_f32": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, _P, _P, _P, _P, c_int32, _P, c_int64, _P, c_int64,
+                                               _P, _P, _P, _P, c_int32, c_int64, _P, _P, _P, _P, _P]),
     "mmrec_gemm_nt_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     "mmrec_topk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "mmrec_score_topk_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P,

@@ -21,6 +21,22 @@
 // arithmetic: fmaxf skips a NaN, which then enters den and acc through exp; +inf gives exp(inf - inf) = NaN; a row of nothing
 // but -inf has no maximum and is set to NaN (exp(-inf + inf) in its alphas): such a row is NaN in every alpha and in Y[r], no
 // other row is touched, and a -inf next to a finite maximum is exactly 0.
+//
+// Backward (mmrec_edge_attention_bwd_f32), from the forward's alpha and Y, in two passes without atomics:
+//     g_p = <dY[r], KV[c]> + dAlpha[p]     t_r = <dY[r], Y[r]> + sum_p alpha_p dAlpha[p]     ds_p = alpha_p (g_p - t_r)
+//     dQ[r] = sum_p ds_p KV[c]             dKV[c] = base[c] + sum over the edges of column c of (alpha_p dY[r] + ds_p Q[r])
+// t_r = sum_p alpha_p g_p is known BEFORE the row is walked, because sum_p alpha_p <dY[r], KV[c_p]> = <dY[r], Y[r]> (Y was built
+// from the same alpha, whatever eps): the dAlpha part is one pass over the row's scalars, never over its 256-byte rows.
+//   row pass     the forward's CSR and access shape: one walk gathers each KV[c] once for g and for dQ; lane t of the group that
+//                handles slots base ... base + 15 writes ds[p] of slot base + t (0 for an absent edge whose position is valid).
+//                A listed row: the 16 groups' dQ states go through LDS and are added in the order g = 0 ... 15, and so are
+//                their parts of sum alpha dAlpha.
+//   column pass  the transposed CSR (rowptr_t, rowidx_t, perm_t): per slot alpha[p] and ds[p] through perm_t, dY[r] and Q[r]
+//                gathered once each; the same group / workgroup split, driven by the column side's list.  base[c] is the first
+//                term of the sum.
+// Every row of dQ and of dKV is written.  A row id outside [0, n_rows) on the transposed side is an absent edge as well.  A row
+// whose alpha is NaN is NaN in its ds, in dQ[r] and in the dKV rows of its columns: the arithmetic's pattern.  Known and
+// accepted, as in the forward: a hub of tens of thousands of edges is ONE workgroup in each pass (no chunk plan here).
 #include "common.h"
 
 #include <math.h>
@@ -182,6 +198,211 @@ __global__ __launch_bounds__(ATT_BLOCK) void edge_attention_block_kernel(
     if (any) write_alpha(start + threadIdx.x, end, ATT_BLOCK, colidx, perm, n_edges, n_kv, m, dn, alpha);
 }
 
+// ------------------------------------------------------------------------------------------------ backward
+// this lane's part of sum_p alpha_p dAlpha_p over the slots first, first + stride, ... of a row (present edges only)
+__device__ __forceinline__ float bwd_alpha_dot(int first, int end, int stride, const int32_t* __restrict__ colidx,
+                                               const int64_t* __restrict__ perm, int n_edges, int n_kv,
+                                               const float* __restrict__ alpha, const float* __restrict__ dAlpha) {
+    float acc = 0.f;
+    for (int j = first; j < end; j += stride) {
+        const int c = colidx[j];
+        const int p = att_pos(perm, j, n_edges);
+        if (c >= 0 && c < n_kv && p >= 0) acc = fmaf(alpha[p], dAlpha[p], acc);
+    }
+    return acc;
+}
+
+// The slots first ... first + 15, first + stride ..., below end, of one row for one 16-lane group, with the row's t known:
+// ds written, ds_p KV[c] added to acc.  gather: dY or dQ is there (without both no source row is needed).
+__device__ __forceinline__ void bwd_row_span(int first, int end, int stride, int t, const int32_t* __restrict__ colidx,
+                                             const int64_t* __restrict__ perm, int n_edges, bool has_dy, float4 dy, float tr,
+                                             const float4* __restrict__ KV4, int n_kv, bool gather,
+                                             const float* __restrict__ alpha, const float* __restrict__ dAlpha,
+                                             float* __restrict__ ds, float4& acc) {
+    for (int base = first; base < end; base += stride) {
+        const int j = base + t;
+        int c = -1, p = -1;
+        float a = 0.f, da = 0.f;
+        if (j < end) {
+            c = colidx[j];
+            p = att_pos(perm, j, n_edges);
+            if (c < 0 || c >= n_kv || p < 0) c = -1;          // an absent edge
+            if (c >= 0) {
+                a = alpha[p];
+                if (dAlpha) da = dAlpha[p];
+            }
+        }
+        const int cnt = min(ATT_GROUP, end - base);
+        float mine = 0.f;
+        for (int k0 = 0; k0 < cnt; k0 += ATT_NB) {
+            float4 x[ATT_NB];
+            int cs[ATT_NB];
+#pragma unroll
+            for (int u = 0; u < ATT_NB; ++u) {
+                cs[u] = __shfl(c, k0 + u, ATT_GROUP);
+                x[u] = (cs[u] >= 0 && gather) ? KV4[(size_t)cs[u] * ATT_GROUP + t] : f4_zero();
+            }
+#pragma unroll
+            for (int u = 0; u < ATT_NB; ++u) {
+                const float gd = has_dy ? row16_sum(f4_dot(dy, x[u])) : 0.f;
+                const float ak = __shfl(a, k0 + u, ATT_GROUP), dak = __shfl(da, k0 + u, ATT_GROUP);
+                if (cs[u] < 0) continue;
+                const float d = ak * ((gd + dak) - tr);
+                acc = f4_fma(d, x[u], acc);
+                if (t == k0 + u) mine = d;
+            }
+        }
+        if (p >= 0) ds[p] = mine;                              // (0 for an absent edge whose position is valid)
+    }
+}
+
+__global__ __launch_bounds__(ATT_BLOCK) void edge_attention_bwd_rows_group_kernel(
+    const int32_t* __restrict__ rowptr, int n_rows, const int32_t* __restrict__ colidx, const int64_t* __restrict__ perm,
+    bool skip_long, const float4* __restrict__ KV4, int n_kv, int n_edges, const float4* __restrict__ Y4,
+    const float* __restrict__ alpha, const float4* __restrict__ dY4, const float* __restrict__ dAlpha, float* __restrict__ ds,
+    float4* __restrict__ dQ4) {
+    const int t = threadIdx.x % ATT_GROUP;
+    const int stride = gridDim.x * ATT_GROUPS;
+    for (long r = (long)blockIdx.x * ATT_GROUPS + threadIdx.x / ATT_GROUP; r < n_rows; r += stride) {
+        int start, end;
+        att_span(rowptr, (int)r, n_edges, start, end);
+        if (skip_long && end - start > ATT_GROUP_MAX) continue;            // the block kernel's
+        float4 dy = f4_zero(), acc = f4_zero();
+        float tr = 0.f;
+        if (dY4) {
+            dy = dY4[(size_t)r * ATT_GROUP + t];
+            tr = row16_sum(f4_dot(dy, Y4[(size_t)r * ATT_GROUP + t]));
+        }
+        if (end > start) {
+            if (dAlpha) tr += row16_sum(bwd_alpha_dot(start + t, end, ATT_GROUP, colidx, perm, n_edges, n_kv, alpha, dAlpha));
+            bwd_row_span(start, end, ATT_GROUP, t, colidx, perm, n_edges, dY4 != nullptr, dy, tr, KV4, n_kv,
+                         dY4 != nullptr || dQ4 != nullptr, alpha, dAlpha, ds, acc);
+        }
+        if (dQ4) dQ4[(size_t)r * ATT_GROUP + t] = acc;
+    }
+}
+
+__global__ __launch_bounds__(ATT_BLOCK) void edge_attention_bwd_rows_block_kernel(
+    const int32_t* __restrict__ rowptr, int n_rows, const int32_t* __restrict__ colidx, const int64_t* __restrict__ perm,
+    const int32_t* __restrict__ long_rows, const float4* __restrict__ KV4, int n_kv, int n_edges, const float4* __restrict__ Y4,
+    const float* __restrict__ alpha, const float4* __restrict__ dY4, const float* __restrict__ dAlpha, float* __restrict__ ds,
+    float* __restrict__ dQ) {
+    __shared__ float s_t[ATT_GROUPS];
+    __shared__ float4 s_acc[ATT_GROUPS][ATT_GROUP];
+    const int r = long_rows[blockIdx.x];
+    if (r < 0 || r >= n_rows) return;                                      // (the whole workgroup)
+    int start, end;
+    att_span(rowptr, r, n_edges, start, end);
+    const int t = threadIdx.x % ATT_GROUP, g = threadIdx.x / ATT_GROUP;
+    float4 dy = f4_zero(), acc = f4_zero();
+    float tr = 0.f;
+    if (dY4) {                                                             // every group: the same bits
+        dy = dY4[(size_t)r * ATT_GROUP + t];
+        tr = row16_sum(f4_dot(dy, Y4[(size_t)r * ATT_GROUP + t]));
+    }
+    if (dAlpha) {                                                          // (a kernel argument: the whole workgroup)
+        const float part = row16_sum(bwd_alpha_dot(start + threadIdx.x, end, ATT_BLOCK, colidx, perm, n_edges, n_kv, alpha, dAlpha));
+        if (t == 0) s_t[g] = part;
+        __syncthreads();
+        float ta = 0.f;
+#pragma unroll
+        for (int k = 0; k < ATT_GROUPS; ++k) ta += s_t[k];                 // in the order g = 0 ... 15
+        tr += ta;
+    }
+    bwd_row_span(start + g * ATT_GROUP, end, ATT_BLOCK, t, colidx, perm, n_edges, dY4 != nullptr, dy, tr, KV4, n_kv,
+                 dY4 != nullptr || dQ != nullptr, alpha, dAlpha, ds, acc);
+    if (!dQ) return;
+    s_acc[g][t] = acc;
+    __syncthreads();
+    if (threadIdx.x < 4 * ATT_GROUP) {                                     // the first wave: one column of dQ[r] per lane
+        const float* col = reinterpret_cast<const float*>(&s_acc[0][0]) + threadIdx.x;
+        float y = 0.f;
+#pragma unroll
+        for (int k = 0; k < ATT_GROUPS; ++k) y += col[k * 4 * ATT_GROUP];
+        dQ[(size_t)r * (4 * ATT_GROUP) + threadIdx.x] = y;
+    }
+}
+
+// The slots of one column for one 16-lane group: acc += alpha_p dY[r] + ds_p Q[r], each row gathered once.
+__device__ __forceinline__ void bwd_col_span(int first, int end, int stride, int t, const int32_t* __restrict__ rowidx_t,
+                                             const int64_t* __restrict__ perm_t, int n_edges, int n_rows,
+                                             const float* __restrict__ alpha, const float* __restrict__ ds,
+                                             const float4* __restrict__ dY4, const float4* __restrict__ Q4, float4& acc) {
+    for (int base = first; base < end; base += stride) {
+        const int j = base + t;
+        int r = -1;
+        float a = 0.f, s = 0.f;
+        if (j < end) {
+            r = rowidx_t[j];
+            const int p = att_pos(perm_t, j, n_edges);
+            if (r < 0 || r >= n_rows || p < 0) {
+                r = -1;                                        // an absent edge
+            } else {
+                a = alpha[p];
+                s = ds[p];
+            }
+        }
+        const int cnt = min(ATT_GROUP, end - base);
+        for (int k0 = 0; k0 < cnt; k0 += ATT_NB) {
+            float4 xd[ATT_NB], xq[ATT_NB];
+            int rs[ATT_NB];
+#pragma unroll
+            for (int u = 0; u < ATT_NB; ++u) {
+                rs[u] = __shfl(r, k0 + u, ATT_GROUP);
+                xd[u] = (rs[u] >= 0 && dY4) ? dY4[(size_t)rs[u] * ATT_GROUP + t] : f4_zero();
+                xq[u] = rs[u] >= 0 ? Q4[(size_t)rs[u] * ATT_GROUP + t] : f4_zero();
+            }
+#pragma unroll
+            for (int u = 0; u < ATT_NB; ++u) {
+                const float ak = __shfl(a, k0 + u, ATT_GROUP), sk = __shfl(s, k0 + u, ATT_GROUP);
+                if (rs[u] < 0) continue;
+                if (dY4) acc = f4_fma(ak, xd[u], acc);
+                acc = f4_fma(sk, xq[u], acc);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(ATT_BLOCK) void edge_attention_bwd_cols_group_kernel(
+    const int32_t* __restrict__ rowptr_t, int n_kv, const int32_t* __restrict__ rowidx_t, const int64_t* __restrict__ perm_t,
+    bool skip_long, int n_rows, int n_edges, const float* __restrict__ alpha, const float* __restrict__ ds,
+    const float4* __restrict__ dY4, const float4* __restrict__ Q4, const float4* __restrict__ base4, float4* __restrict__ dKV4) {
+    const int t = threadIdx.x % ATT_GROUP;
+    const int stride = gridDim.x * ATT_GROUPS;
+    for (long c = (long)blockIdx.x * ATT_GROUPS + threadIdx.x / ATT_GROUP; c < n_kv; c += stride) {
+        int start, end;
+        att_span(rowptr_t, (int)c, n_edges, start, end);
+        if (skip_long && end - start > ATT_GROUP_MAX) continue;            // the block kernel's
+        float4 acc = base4 ? base4[(size_t)c * ATT_GROUP + t] : f4_zero();
+        if (end > start) bwd_col_span(start, end, ATT_GROUP, t, rowidx_t, perm_t, n_edges, n_rows, alpha, ds, dY4, Q4, acc);
+        dKV4[(size_t)c * ATT_GROUP + t] = acc;
+    }
+}
+
+__global__ __launch_bounds__(ATT_BLOCK) void edge_attention_bwd_cols_block_kernel(
+    const int32_t* __restrict__ rowptr_t, int n_kv, const int32_t* __restrict__ rowidx_t, const int64_t* __restrict__ perm_t,
+    const int32_t* __restrict__ long_cols, int n_rows, int n_edges, const float* __restrict__ alpha,
+    const float* __restrict__ ds, const float4* __restrict__ dY4, const float4* __restrict__ Q4, const float* __restrict__ base,
+    float* __restrict__ dKV) {
+    __shared__ float4 s_acc[ATT_GROUPS][ATT_GROUP];
+    const int c = long_cols[blockIdx.x];
+    if (c < 0 || c >= n_kv) return;                                        // (the whole workgroup)
+    int start, end;
+    att_span(rowptr_t, c, n_edges, start, end);
+    const int t = threadIdx.x % ATT_GROUP, g = threadIdx.x / ATT_GROUP;
+    float4 acc = f4_zero();
+    bwd_col_span(start + g * ATT_GROUP, end, ATT_BLOCK, t, rowidx_t, perm_t, n_edges, n_rows, alpha, ds, dY4, Q4, acc);
+    s_acc[g][t] = acc;
+    __syncthreads();
+    if (threadIdx.x < 4 * ATT_GROUP) {                                     // the first wave: one column of dKV[c] per lane
+        const float* col = reinterpret_cast<const float*>(&s_acc[0][0]) + threadIdx.x;
+        float y = base ? base[(size_t)c * (4 * ATT_GROUP) + threadIdx.x] : 0.f;
+#pragma unroll
+        for (int k = 0; k < ATT_GROUPS; ++k) y += col[k * 4 * ATT_GROUP];
+        dKV[(size_t)c * (4 * ATT_GROUP) + threadIdx.x] = y;
+    }
+}
+
 }  // namespace
 
 extern "C" int32_t mmrec_edge_attention_group_max(void) { return ATT_GROUP_MAX; }
@@ -206,5 +427,45 @@ extern "C" int mmrec_edge_attention_f32(const int32_t* rowptr, int32_t n_rows, c
         hipLaunchKernelGGL(edge_attention_block_kernel, dim3(n_long), dim3(ATT_BLOCK), 0, s, rowptr, (int)n_rows, colidx, perm,
                            long_rows, reinterpret_cast<const float4*>(Q), reinterpret_cast<const float4*>(KV), (int)n_kv,
                            (int)n_edges, eps, Y, alpha);
+    MMREC_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int mmrec_edge_attention_bwd_f32(const int32_t* rowptr, int32_t n_rows, const int32_t* colidx, const int64_t* perm,
+                                            const int32_t* long_rows, int32_t n_long, const int32_t* rowptr_t,
+                                            const int32_t* rowidx_t, const int64_t* perm_t, const int32_t* long_cols,
+                                            int32_t n_long_t, const float* Q, int64_t n_q, const float* KV, int64_t n_kv,
+                                            const float* Y, const float* alpha, const float* dY, const float* dAlpha, int32_t d,
+                                            int64_t n_edges, float* ds, float* dQ, float* dKV, const float* dKV_base,
+                                            mmrec_stream_t stream) {
+    if (d != 4 * ATT_GROUP) return MMREC_ERR_UNSUPPORTED;
+    if (n_rows < 0 || n_edges < 0 || n_long < 0 || n_long_t < 0 || n_q < 0 || n_kv < 0) return MMREC_ERR_BAD_ARG;
+    if (n_rows == 0 || n_edges == 0) return 0;                             // nothing to launch (the caller's zeros stand)
+    if (n_edges > INT32_MAX || n_kv > INT32_MAX) return MMREC_ERR_UNSUPPORTED;
+    if (n_q < n_rows) return MMREC_ERR_BAD_ARG;
+    if (!rowptr || !colidx || !KV || !alpha || !ds) return MMREC_ERR_BAD_ARG;
+    if ((!dY && !dAlpha) || (dY && !Y) || (!dQ && !dKV)) return MMREC_ERR_BAD_ARG;
+    if (dKV && (!rowptr_t || !rowidx_t || !Q || dKV_base == dKV)) return MMREC_ERR_BAD_ARG;
+    if ((n_long > 0 && !long_rows) || (dKV && n_long_t > 0 && !long_cols)) return MMREC_ERR_BAD_ARG;
+    hipStream_t s = mmrec_stream(stream);
+    const float4 *KV4 = reinterpret_cast<const float4*>(KV), *Y4 = reinterpret_cast<const float4*>(Y),
+                 *dY4 = reinterpret_cast<const float4*>(dY);
+    int blocks = (n_rows + ATT_GROUPS - 1) / ATT_GROUPS;
+    hipLaunchKernelGGL(edge_attention_bwd_rows_group_kernel, dim3(blocks < ATT_MAX_BLOCKS ? blocks : ATT_MAX_BLOCKS),
+                       dim3(ATT_BLOCK), 0, s, rowptr, (int)n_rows, colidx, perm, n_long > 0, KV4, (int)n_kv, (int)n_edges, Y4, alpha,
+                       dY4, dAlpha, ds, reinterpret_cast<float4*>(dQ));
+    if (n_long > 0)
+        hipLaunchKernelGGL(edge_attention_bwd_rows_block_kernel, dim3(n_long), dim3(ATT_BLOCK), 0, s, rowptr, (int)n_rows, colidx,
+                           perm, long_rows, KV4, (int)n_kv, (int)n_edges, Y4, alpha, dY4, dAlpha, ds, dQ);
+    if (dKV && n_kv > 0) {
+        blocks = (int)((n_kv + ATT_GROUPS - 1) / ATT_GROUPS);
+        hipLaunchKernelGGL(edge_attention_bwd_cols_group_kernel, dim3(blocks < ATT_MAX_BLOCKS ? blocks : ATT_MAX_BLOCKS),
+                           dim3(ATT_BLOCK), 0, s, rowptr_t, (int)n_kv, rowidx_t, perm_t, n_long_t > 0, (int)n_rows, (int)n_edges,
+                           alpha, ds, dY4, reinterpret_cast<const float4*>(Q), reinterpret_cast<const float4*>(dKV_base),
+                           reinterpret_cast<float4*>(dKV));
+        if (n_long_t > 0)
+            hipLaunchKernelGGL(edge_attention_bwd_cols_block_kernel, dim3(n_long_t), dim3(ATT_BLOCK), 0, s, rowptr_t, (int)n_kv,
+                               rowidx_t, perm_t, long_cols, (int)n_rows, (int)n_edges, alpha, ds, dY4,
+                               reinterpret_cast<const float4*>(Q), dKV_base, dKV);
+    }
     MMREC_RETURN_LAUNCH_STATUS();
 }

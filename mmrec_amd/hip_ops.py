@@ -2102,6 +2102,7 @@ def edge_softmax(score, dyn, by="row", eps=1e-16):
 # Fused edge attention (mmrec_edge_attention_f32): edge_dot -> edge_softmax -> spmm_vals in one pass over the edges
 # ------------------------------------------------------------------------------------------------
 EDGE_ATTENTION = True   # False: every edge_attention call is the three-op composition (A/B runs)
+EDGE_ATTENTION_BWD = True   # False: edge_attention(fused_backward=True) takes the backward composed of the older kernels (A/B runs)
 
 
 def edge_attention_group_max():
@@ -2134,10 +2135,10 @@ def _spmm_with(g, vals, X):
 
 
 class _EdgeAttention(torch.autograd.Function):
-    """forward(Q, KV or None for `Q is KV`, dyn, eps) -> (Y, alpha)"""
+    """forward(Q, KV or None for `Q is KV`, dyn, eps, fused_backward) -> (Y, alpha)"""
 
     @staticmethod
-    def forward(ctx, Q, KV, dyn, eps):
+    def forward(ctx, Q, KV, dyn, eps, fused_backward=False):
         ctx.same = KV is None
         if ctx.same:
             KV = Q
@@ -2151,18 +2152,37 @@ class _EdgeAttention(torch.autograd.Function):
                                                         _p(Q), Q.shape[0], _p(KV), KV.shape[0], EMB_DIM, n_edges, eps, _p(Y),
                                                         _p(alpha), _stream()), "edge_attention")
         ctx.dyn = dyn
+        ctx.fused_backward = bool(fused_backward and EDGE_ATTENTION_BWD)
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(Q, KV, alpha)
+        if ctx.fused_backward:
+            _softmax_side(dyn, "col")                           # the column side's list: host work, so here and not in backward
+            ctx.save_for_backward(Q, KV, alpha, Y)
+        else:
+            ctx.save_for_backward(Q, KV, alpha)
         return Y, alpha
 
     @staticmethod
     def backward(ctx, dY, dA):
-        Q, KV, alpha = ctx.saved_tensors
+        Q, KV, alpha = ctx.saved_tensors[:3]
         dyn, same = ctx.dyn, ctx.same
         want_q, want_kv = ctx.needs_input_grad[0], (ctx.needs_input_grad[0] if same else ctx.needs_input_grad[1])
         if (dY is None and dA is None) or not (want_q or want_kv) or not alpha.numel():
             zq = torch.zeros_like(Q) if want_q else None
-            return zq, (None if same or not want_kv else torch.zeros_like(KV)), None, None
+            return zq, (None if same or not want_kv else torch.zeros_like(KV)), None, None, None
+        if ctx.fused_backward:                                  # one call: ds, dQ and dKV with every row gathered once
+            fwd, perm, long_rows = _softmax_side(dyn, "row")    # (both lists are cached since the forward)
+            bwd, perm_t, long_cols = _softmax_side(dyn, "col")
+            dY = None if dY is None else dY.contiguous()
+            dA = None if dA is None else dA.contiguous()
+            ds = torch.empty_like(alpha)
+            dQ = torch.empty_like(Q) if want_q else None
+            dKV = torch.empty_like(KV) if want_kv else None
+            _lib.check(_lib.load().mmrec_edge_attention_bwd_f32(
+                _p(fwd.rowptr), fwd.n_rows, _p(fwd.colidx), _p(perm), _p(long_rows), 0 if long_rows is None else long_rows.numel(),
+                _p(bwd.rowptr), _p(bwd.colidx), _p(perm_t), _p(long_cols), 0 if long_cols is None else long_cols.numel(),
+                _p(Q), Q.shape[0], _p(KV), KV.shape[0], _p(ctx.saved_tensors[3]), _p(alpha), _p(dY), _p(dA), EMB_DIM,
+                alpha.numel(), _p(ds), _p(dQ), _p(dKV), _p(dQ) if same else None, _stream()), "edge_attention_bwd")
+            return (dKV if same else dQ), (None if same else dKV), None, None, None
         # d alpha_e = <dY[row_e], KV[col_e]> (+ what arrives at alpha itself); through the softmax from the saved alpha
         g = None
         if dY is not None:
@@ -2184,11 +2204,11 @@ class _EdgeAttention(torch.autograd.Function):
             if dY is not None:
                 dKV = _spmm_with(dyn.bwd, alpha[dyn.perm_t].contiguous(), dY) + dKV
         if same:
-            return dQ + dKV, None, None, None
-        return dQ, dKV, None, None
+            return dQ + dKV, None, None, None, None
+        return dQ, dKV, None, None, None
 
 
-def edge_attention(Q, KV, dyn, eps=1e-16):
+def edge_attention(Q, KV, dyn, eps=1e-16, fused_backward=False):
     """Attention over the edges of `dyn` ("GAT aggregation"): for every edge e = (row, col) the score s_e = <Q[row], KV[col]>,
     alpha = the softmax of the scores over the edges that share a row (eps in the denominator), Y[row] = sum_e alpha_e KV[col];
     -> (Y [n_rows, 64], alpha [n_edges] in the order of dyn's edge list).  GRCN's content GCN (grcn.py:63-72).
@@ -2200,10 +2220,16 @@ def edge_attention(Q, KV, dyn, eps=1e-16):
     gradient arriving at alpha), ds = the segment softmax's backward, dQ = SpMM(dyn.fwd, ds) KV, dKV = SpMM(dyn.bwd, alpha) dY +
     SpMM(dyn.bwd, ds) Q; `Q is KV`: the two are summed.  The long-row list is built on the host at the first call on a DynGraph:
     call once before capturing a step.
+    `fused_backward=True` (and the `EDGE_ATTENTION_BWD` switch on; ignored where the kernel does not serve): Y is saved as well
+    and the backward is ONE call, mmrec_edge_attention_bwd_f32 -- the row's sum of alpha g is <dY[r], Y[r]> (+ sum alpha dAlpha),
+    known before the row is walked, so a row pass gathers each KV[col] once for ds and dQ and a column pass over dyn.bwd gathers
+    dY[row] and Q[row] once each for dKV, reading alpha and ds through perm_t: three row gathers per edge instead of five, one
+    [n_edges] intermediate instead of six, no atomics (fixed bits); `Q is KV`: dQ enters the column pass as its first term.  Both
+    long lists are built in the FORWARD, so the backward does no host work.
     EVERY OTHER CASE (CPU tensors, other widths or dtypes, non-contiguous tables, table lengths that are not dyn's, the switch
     off) is exactly `edge_dot` -> `edge_softmax` -> `spmm_vals` with stock autograd."""
     if edge_attention_served(Q, KV, dyn):
-        return _EdgeAttention.apply(Q, None if Q is KV else KV, dyn, float(eps))
+        return _EdgeAttention.apply(Q, None if Q is KV else KV, dyn, float(eps), bool(fused_backward))
     alpha = edge_softmax(edge_dot(Q, KV, dyn.rows, dyn.cols, dyn=dyn), dyn, eps=eps)
     return spmm_vals(dyn, KV, alpha), alpha
 

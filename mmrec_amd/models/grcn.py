@@ -9,7 +9,8 @@ list never changes; the per-edge scores are the SDDMM kernel (`hip_ops.edge_dot`
 structure), the segment softmax over a target's incoming edges is `hip_ops.edge_softmax` over the same structure's CSR
 form (no atomics: the attention weights and their gradient repeat bit for bit).  With the config key `fused_attention: True`
 (absent / False: the three ops) the content GCN's attention is `hip_ops.edge_attention`: scores, softmax and aggregation in one
-kernel that gathers every source row once.  BPR runs on the fused kernel over the 192-wide concatenation, evaluation on the fused score + mask +
+kernel that gathers every source row once; with `fused_attention_backward: True` as well (absent / False: the backward composed
+of the older kernels) its backward is one call too (`mmrec_edge_attention_bwd_f32`).  BPR runs on the fused kernel over the 192-wide concatenation, evaluation on the fused score + mask +
 top-K.
 
 Reference behaviour kept:
@@ -52,9 +53,10 @@ class EGCN(nn.Module):
 class CGCN(nn.Module):
     """content embeddings of one modality + the attention weight of every (bidirectional) edge"""
 
-    def __init__(self, features, num_user, dim_C, num_routing, fused_attention=False):
+    def __init__(self, features, num_user, dim_C, num_routing, fused_attention=False, fused_attention_backward=False):
         super().__init__()
         self.num_user, self.num_routing, self.fused_attention = num_user, num_routing, bool(fused_attention)
+        self.fused_attention_backward = bool(fused_attention_backward)       # only read together with fused_attention
         self.preference = nn.Parameter(nn.init.xavier_normal_(torch.rand((num_user, dim_C))))
         self.features = features
         self.MLP = nn.Linear(features.size(1), dim_C)
@@ -67,7 +69,7 @@ class CGCN(nn.Module):
             preference = F.normalize(preference)          # + the all-zero user rows of the item-side aggregation
         x = torch.cat((preference, features), dim=0)
         if self.fused_attention:                          # scores, softmax and aggregation in one pass over the edges
-            agg, alpha = hip_ops.edge_attention(x, x, edges.dyn)
+            agg, alpha = hip_ops.edge_attention(x, x, edges.dyn, fused_backward=self.fused_attention_backward)
             return x + agg, alpha
         score = hip_ops.edge_dot(x, x, edges.dst, edges.src, dyn=edges.dyn)
         alpha = hip_ops.edge_softmax(score, edges.dyn)
@@ -99,12 +101,13 @@ class GRCN(FusedEvalMixin, GeneralRecommender):
         self.edges = _Edges(users, items, n, self.device)
         self.id_gcn = EGCN(self.n_users, self.n_items, dim_x)
         fused = bool(config['fused_attention'])           # new key, default off: `hip_ops.edge_attention` for the content GCNs
+        fused_bwd = bool(config['fused_attention_backward'])      # new key, default off: the attention's backward in one call
         num_model = 0
         if self.v_feat is not None:
-            self.v_gcn = CGCN(self.v_feat, self.n_users, dim_C, config['n_layers'], fused)
+            self.v_gcn = CGCN(self.v_feat, self.n_users, dim_C, config['n_layers'], fused, fused_bwd)
             num_model += 1
         if self.t_feat is not None:
-            self.t_gcn = CGCN(self.t_feat, self.n_users, dim_C, config['n_layers'], fused)
+            self.t_gcn = CGCN(self.t_feat, self.n_users, dim_C, config['n_layers'], fused, fused_bwd)
             num_model += 1
         if num_model == 0:
             raise ValueError("GRCN needs at least one item feature modality")

@@ -149,6 +149,29 @@ int mmrec_spmm_csr_sched_f32_layergcn(const int32_t* rowptr, const int32_t* coli
 int mmrec_spmm_row_keys(const int32_t* rowptr, const int32_t* colidx, const int32_t* col_degree, int32_t n_rows,
                         int32_t long_row_threshold, int32_t key_deg_max, int32_t* key, int32_t* key_degree,
                         mmrec_stream_t stream);
+
+/* Edge dropout inside the product (common/encoders.py:77-103: sparse_dropout of the normalised adjacency, drawn per batch).
+ * ADDITIVE to ABI 16: two new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * The mask is ONE BIT PER CSR ENTRY in the order of the CSR the launch runs on: entry k is bit (k & 31) of the 32-bit word
+ * keep_bits[k >> 5] ((nnz + 31) / 32 words); a set bit means kept.
+ * mmrec_spmm_csr_masked_f32 is mmrec_spmm_csr_f32 -- arguments, plan (the FULL graph's: thresholds, chunk boundaries, tickets,
+ * the two-launch finish without them), epilogue -- on the matrix in which entry k has the value vals[k] * val_scale (one fp32
+ * multiply) if its bit is set and is ABSENT otherwise: its source row is never gathered.  A row's kept entries are added in
+ * CSR order at the positions the unmasked launch adds them, so
+ *   - with every bit set and val_scale = 1 the result is bit-identical to mmrec_spmm_csr_f32;
+ *   - for finite X it equals, as numbers, mmrec_spmm_csr_f32 on the value vector whose dropped entries are +0;
+ *   - a dropped entry whose source row holds inf / NaN contributes nothing (the zero-valued form gives NaN).
+ * d: a multiple of 64 up to 384; the 8 / 16 / 32-column slices are not served (MMREC_ERR_UNSUPPORTED).
+ * mmrec_edge_keep_bits packs a keep vector (one byte per entry, nonzero = kept, the caller's edge order) for up to two entry
+ * orders in one launch: bit j of bits_x = keep[perm_x[j]] (perm_x int64 [n_edges], NULL = identity; bits_b NULL = one
+ * output only).  Bits at positions >= n_edges of the last word are written as zero.  n_edges = 0 launches nothing. */
+int mmrec_spmm_csr_masked_f32(const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* X, float* Y,
+                              const float* Z, const float* acc_in, float* acc_out, int32_t n_rows, int32_t d, float alpha,
+                              float beta, float acc_scale, int32_t long_row_threshold, const int32_t* long_rows,
+                              const int32_t* long_chunk_ptr, int32_t n_long, int32_t n_chunks, float* partials,
+                              int32_t* long_tickets, const uint32_t* keep_bits, float val_scale, mmrec_stream_t stream);
+int mmrec_edge_keep_bits(const uint8_t* keep, int64_t n_edges, const int64_t* perm_a, uint32_t* bits_a,
+                         const int64_t* perm_b, uint32_t* bits_b, mmrec_stream_t stream);
 /* Host-side plan helpers (pure CPU, rowptr is a HOST pointer).  count: returns n_long and n_chunks;
  * fill: writes long_rows[n_long] and long_chunk_ptr[n_long+1] (host arrays the caller copies to the
  * device).  partials workspace = n_chunks * d * 4 bytes (d: the row width of the SpMM call). */

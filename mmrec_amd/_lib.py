@@ -33,6 +33,9 @@ SIGNATURES = {
                                            _P, _P, _P, _P, c_int32, _P]),
     "mmrec_spmm_csr_sched_f32_layergcn": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32,
                                                     _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P]),
+    "mmrec_spmm_csr_masked_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_float,
+                                            c_float, c_float, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P, c_float, _P]),
+    "mmrec_edge_keep_bits": (c_int32, [_P, c_int64, _P, _P, _P, _P, _P]),
     "mmrec_spmm_row_keys": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P]),
     "mmrec_spmm_plan_count": (c_int32, [_P, c_int32, c_int32, _P, _P]),
     "mmrec_spmm_plan_fill": (c_int32, [_P, c_int32, c_int32, _P, _P]),

@@ -5,6 +5,10 @@ LightGCN_Encoder: mean_l(A_hat^l E0) with A_hat = sparse_dropout(norm_adj, rate 
 values do, so one `DynGraph` (structure + transpose permutation, built once) serves every batch and the dropped
 entries are zeros of the value vector; the masked matrix is not symmetric, the backward runs on the transposed CSR
 with the same values.  `get_embedding` (no dropout) is the fused layer-mean SpMM on the plain normalised CSR.
+
+`fused_edge_dropout: True` (config key, off by default): the dropout branch runs `hip_ops.lightgcn_mean_edge_dropout` -- the
+keep mask packed to one bit per entry, dropped entries never gathered, the layer mean in the SpMM's accumulator epilogue (the
+arithmetic of the no-dropout path, not the bits of `stack().mean()`).  The draws are the same either way.
 """
 import numpy as np
 import torch
@@ -31,6 +35,8 @@ class LightGCN_Encoder(GeneralRecommender):
             'item_emb': nn.Parameter(init(torch.empty(self.item_count, self.latent_size)))})
         self.sparse_norm_adj = norm_adj_graph(self.interaction_matrix, self.n_users, self.n_items, self.device)
         self._dyn = None
+        self.fused_edge_dropout = bool(config['fused_edge_dropout']) if 'fused_edge_dropout' in config else False
+        self._edge_graph = None
 
     def draw_dropout(self):
         """(rate, keep mask over the nnz entries in row-major order) -- encoders.py:77-79,86-88."""
@@ -48,10 +54,26 @@ class LightGCN_Encoder(GeneralRecommender):
         rate, keep = self.draw_dropout()
         return self._dyn, (g.vals * keep.to(g.vals.dtype)) * (1. / (1 - rate))
 
+    def _edge_dropout_graph(self):
+        """the fixed normalised values on the structure `_dropped_values` uses, built once, next to `_dyn`"""
+        g = self.sparse_norm_adj
+        if self._edge_graph is None:
+            if self._dyn is None:
+                n = g.n_rows
+                rows = torch.repeat_interleave(torch.arange(n, device=g.rowptr.device), torch.diff(g.rowptr.to(torch.int64)))
+                self._dyn = hip_ops.DynGraph(rows.contiguous(), g.colidx.to(torch.int64).contiguous(), n, n,
+                                             long_row_threshold=g.long_row_threshold)
+            self._edge_graph = hip_ops.EdgeDropoutGraph(self._dyn, g.vals)
+        return self._edge_graph
+
     def all_embeddings(self, dropout):
         ego = torch.cat([self.embedding_dict['user_emb'], self.embedding_dict['item_emb']], 0)
         if not dropout:
             out = hip_ops.lightgcn_mean(self.sparse_norm_adj, ego, self.n_layers)
+        elif self.fused_edge_dropout:
+            eg = self._edge_dropout_graph()
+            rate, keep = self.draw_dropout()
+            out = hip_ops.lightgcn_mean_edge_dropout(eg, ego, self.n_layers, keep, 1. / (1 - rate))
         else:
             dyn, vals = self._dropped_values()
             layers = [ego]

@@ -318,6 +318,178 @@ void launch_spmm(hipStream_t s, int blocks, int nch, const int32_t* rowptr, cons
                            long_chunk_ptr, n_long, partials, ep);
 }
 
+// ---- Edge dropout inside the product (encoders.py:77-103): one keep bit per CSR entry ------------------------------
+// Entry k is bit (k & 31) of keep_bits[k >> 5]; a set bit keeps the entry with value vals[k] * val_scale (one fp32 multiply),
+// a clear bit REMOVES it: its column id is never used, its X row never gathered (a zero-valued entry would still cost the
+// 256-B gather, and turn an inf / NaN source row into NaN).
+//
+// gather_span with the mask: the 16 lanes read the 16 keep bits of their span next to the indices, the group takes its 16 bits
+// out of the wave's ballot and walks the SET bits in ascending position -- CSR order -- up to NB gathers in flight.  The bit
+// mask is the same in all 16 lanes of a group, so they run the same trip counts and the shuffles read lanes of the own group
+// only; other groups of the wave may be in another trip or done: their ballot bits are not looked at.  With every bit set
+// and val_scale = 1 this is gather_span operation for operation (the padding slots of a step are fma(0, 0, acc) in both).
+template <int DCH>
+__device__ __forceinline__ void gather_span_masked(const int32_t* __restrict__ colidx, const float* __restrict__ vals,
+                                                   const uint32_t* __restrict__ keep_bits, float val_scale,
+                                                   const float4* __restrict__ X4, int s, int e, int lane16,
+                                                   float4 (&acc)[DCH]) {
+    constexpr int NB = DCH == 1 ? 8 : (DCH <= 2 ? 4 : (DCH <= 4 ? 2 : 1));
+    const int gshift = threadIdx.x & 48;  // where the group's 16 lanes sit in the wave
+    for (int base = s; base < e; base += 16) {
+        const int k = base + lane16;
+        int c = 0;
+        float v = 0.f;
+        bool kept = false;
+        if (k < e) {  // lanes past the span read neither the indices nor the mask
+            kept = (keep_bits[k >> 5] >> (k & 31)) & 1u;
+            c = colidx[k];
+            v = vals[k] * val_scale;
+        }
+        unsigned m = (unsigned)(__ballot(kept) >> gshift) & 0xffffu;
+        while (m) {  // uniform within the group
+            float4 x[NB][DCH];
+            float vv[NB];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                const bool on = m != 0;
+                const int j = on ? __ffs(m) - 1 : 0;
+                m &= m - 1;
+                const int cj = __shfl(c, j, 16);
+                const float vj = __shfl(v, j, 16);
+                vv[u] = on ? vj : 0.f;
+#pragma unroll
+                for (int ch = 0; ch < DCH; ++ch)
+                    x[u][ch] = on ? X4[(size_t)cj * (16 * DCH) + ch * 16 + lane16] : f4_zero();
+            }
+#pragma unroll
+            for (int u = 0; u < NB; ++u)
+#pragma unroll
+                for (int ch = 0; ch < DCH; ++ch) acc[ch] = f4_fma(vv[u], x[u][ch], acc[ch]);
+        }
+    }
+}
+
+// spmm_rows_kernel<DCH, false, false> with the mask: the same blocks, spans, chunk boundaries, tickets and finish -- the plan
+// is the FULL graph's, so a row's kept entries are summed in the order the unmasked launch sums them.  A kernel of its own
+// (not one more template flag): the unmasked instantiations stay what they were, register for register.
+template <int DCH>
+__global__ __launch_bounds__(256) void spmm_rows_masked_kernel(
+    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx, const float* __restrict__ vals,
+    const uint32_t* __restrict__ keep_bits, float val_scale, const float* __restrict__ X, RowEpilogue ep, int n_rows,
+    int long_t, int rows_per_group, const int32_t* __restrict__ long_rows, const int32_t* __restrict__ long_chunk_ptr,
+    int n_long, int n_chunks, float* __restrict__ partials, int32_t* __restrict__ tickets) {
+    __shared__ float4 red[16][16 * DCH];
+    __shared__ int s_last;
+    const int lane16 = threadIdx.x & 15;
+    const int g = threadIdx.x >> 4;
+    const float4* X4 = reinterpret_cast<const float4*>(X);
+    if ((int)blockIdx.x < n_chunks) {
+        const int chunk = blockIdx.x;
+        int lo = 0, hi = n_long;  // largest lo with long_chunk_ptr[lo] <= chunk
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (long_chunk_ptr[mid] <= chunk) lo = mid; else hi = mid;
+        }
+        const int row = long_rows[lo];
+        const int cs = rowptr[row] + (chunk - long_chunk_ptr[lo]) * MMREC_SPMM_CHUNK;
+        const int ce = min(cs + MMREC_SPMM_CHUNK, rowptr[row + 1]);
+        float4 acc[DCH];
+#pragma unroll
+        for (int ch = 0; ch < DCH; ++ch) acc[ch] = f4_zero();
+        for (int base = cs + g * 16; base < ce; base += 256)
+            gather_span_masked<DCH>(colidx, vals, keep_bits, val_scale, X4, base, min(base + 16, ce), lane16, acc);
+#pragma unroll
+        for (int ch = 0; ch < DCH; ++ch) red[g][ch * 16 + lane16] = acc[ch];
+        __syncthreads();
+        const int c0 = long_chunk_ptr[lo], c1 = long_chunk_ptr[lo + 1];
+        if (g == 0) {
+            float4 t[DCH];
+#pragma unroll
+            for (int ch = 0; ch < DCH; ++ch) {
+                t[ch] = red[0][ch * 16 + lane16];
+#pragma unroll
+                for (int i = 1; i < 16; ++i) t[ch] = f4_add(t[ch], red[i][ch * 16 + lane16]);
+            }
+            if (c1 - c0 == 1) {
+                store_row<DCH, false>(ep, row, lane16, t);
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < DCH; ++ch) {
+                    float4* dst = reinterpret_cast<float4*>(partials) + (size_t)chunk * (16 * DCH) + ch * 16 + lane16;
+                    if (tickets) st_coherent(dst, t[ch]); else *dst = t[ch];
+                }
+            }
+        }
+        if (!tickets || c1 - c0 == 1) return;     // uniform
+        if (threadIdx.x < 64) {                    // the hand-off of spmm_rows_kernel, see there
+            __atomic_signal_fence(__ATOMIC_SEQ_CST);
+            __builtin_amdgcn_s_waitcnt(0);
+            __atomic_signal_fence(__ATOMIC_SEQ_CST);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (threadIdx.x == 0)
+                s_last = __hip_atomic_fetch_add(tickets + lo, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == c1 - c0 - 1;
+        }
+        __syncthreads();
+        if (!s_last) return;                       // uniform
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        reduce_long_row<DCH, true, false>(partials, c0, c1, row, ep, red);
+        if (threadIdx.x == 0) __hip_atomic_store(tickets + lo, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const int row0 = ((int)blockIdx.x - n_chunks) * 16 * rows_per_group + g;
+#pragma unroll 1
+    for (int i = 0; i < rows_per_group; ++i) {
+        const int row = row0 + i * 16;
+        if (row >= n_rows) break;
+        const int s = rowptr[row], e = rowptr[row + 1];
+        if (e - s > long_t) continue;  // handled by the chunk blocks
+        float4 acc[DCH];
+#pragma unroll
+        for (int ch = 0; ch < DCH; ++ch) acc[ch] = f4_zero();
+        gather_span_masked<DCH>(colidx, vals, keep_bits, val_scale, X4, s, e, lane16, acc);
+        store_row<DCH, false>(ep, row, lane16, acc);
+    }
+}
+
+template <int DCH>
+void launch_spmm_masked(hipStream_t s, int blocks, int nch, const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                        const uint32_t* keep_bits, float val_scale, const float* X, const RowEpilogue& ep, int n_rows,
+                        int long_t, int rows_per_group, const int32_t* long_rows, const int32_t* long_chunk_ptr, int n_long,
+                        float* partials, int32_t* tickets) {
+    if (blocks + nch > 0)
+        hipLaunchKernelGGL((spmm_rows_masked_kernel<DCH>), dim3(blocks + nch), dim3(256), 0, s, rowptr, colidx, vals,
+                           keep_bits, val_scale, X, ep, n_rows, long_t, rows_per_group, long_rows, long_chunk_ptr, n_long, nch,
+                           partials, tickets);
+    if (!tickets && n_long > 0 && nch > n_long)  // the partials are plain sums: the unmasked finish serves them
+        hipLaunchKernelGGL((spmm_long_reduce_kernel<DCH, false>), dim3(n_long), dim3(256), 0, s, long_rows,
+                           long_chunk_ptr, n_long, partials, ep);
+}
+
+// keep [E] (one byte per entry, caller's edge order) -> packed words in up to two entry orders: bits_x[j] = keep[perm_x[j]]
+// (perm_x NULL: identity).  One ballot per 64 entries; lane 0 of the wave writes its two words with ordinary stores.  The
+// grid covers whole words, lanes at positions >= E vote 0: the trailing bits of the last word are zero.
+__global__ __launch_bounds__(256) void edge_keep_bits_kernel(const uint8_t* __restrict__ keep, long long n_edges,
+                                                             const int64_t* __restrict__ perm_a,
+                                                             uint32_t* __restrict__ bits_a,
+                                                             const int64_t* __restrict__ perm_b,
+                                                             uint32_t* __restrict__ bits_b) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long n_words = (n_edges + 31) >> 5;
+    const long long w = (j >> 6) * 2;  // the wave's first word
+    const bool in = j < n_edges;
+    const unsigned long long a = __ballot(in && keep[perm_a ? perm_a[j] : j] != 0);
+    unsigned long long b = 0;
+    if (bits_b) b = __ballot(in && keep[perm_b ? perm_b[j] : j] != 0);  // uniform
+    if ((threadIdx.x & 63) == 0 && w < n_words) {
+        bits_a[w] = (uint32_t)a;
+        if (w + 1 < n_words) bits_a[w + 1] = (uint32_t)(a >> 32);
+        if (bits_b) {
+            bits_b[w] = (uint32_t)b;
+            if (w + 1 < n_words) bits_b[w + 1] = (uint32_t)(b >> 32);
+        }
+    }
+}
+
 // ---- LayerGCN per-layer cosine re-weighting (layergcn.py:132-134) -------------------------------
 __global__ __launch_bounds__(256) void cos_scale_fwd_kernel(const float* __restrict__ E,
                                                             const float* __restrict__ Ego,
@@ -450,6 +622,56 @@ extern "C" int mmrec_spmm_csr_f32(const int32_t* rowptr, const int32_t* colidx, 
         MMREC_SPMM_CASE(6)
     }
 #undef MMREC_SPMM_CASE
+    MMREC_RETURN_LAUNCH_STATUS();
+}
+
+// The product with edge dropout inside (additive to ABI 16): the argument checks of mmrec_spmm_csr_f32, then its launch
+// shape with spmm_rows_masked_kernel.  64 k-wide rows only; the feature slices have no masked form.
+extern "C" int mmrec_spmm_csr_masked_f32(const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                                         const float* X, float* Y, const float* Z, const float* acc_in,
+                                         float* acc_out, int32_t n_rows, int32_t d, float alpha, float beta,
+                                         float acc_scale, int32_t long_row_threshold,
+                                         const int32_t* long_rows, const int32_t* long_chunk_ptr,
+                                         int32_t n_long, int32_t n_chunks, float* partials, int32_t* long_tickets,
+                                         const uint32_t* keep_bits, float val_scale, mmrec_stream_t stream) {
+    if (d <= 0 || d % MMREC_EMB_DIM || d / MMREC_EMB_DIM > 6) return MMREC_ERR_UNSUPPORTED;
+    if (n_rows < 0 || n_long < 0 || n_chunks < 0 || long_row_threshold < 0) return MMREC_ERR_BAD_ARG;
+    if (n_rows == 0) return 0;
+    if (!rowptr || !X || !keep_bits || (!Y && !acc_out)) return MMREC_ERR_BAD_ARG;
+    if (acc_out && !acc_in) return MMREC_ERR_BAD_ARG;
+    if (n_long > 0 && (!long_rows || !long_chunk_ptr || !partials || n_chunks <= 0))
+        return MMREC_ERR_BAD_ARG;
+    if (Y == X || acc_out == X) return MMREC_ERR_BAD_ARG;  // other rows still gather from X
+    RowEpilogue ep{Z, Y, acc_in, acc_out, alpha, Z ? beta : 0.f, acc_scale, nullptr, nullptr, nullptr};
+    hipStream_t s = mmrec_stream(stream);
+    const int rows_per_group = MMREC_SPMM_RPG(n_rows);
+    const int blocks = (n_rows + 16 * rows_per_group - 1) / (16 * rows_per_group);
+    const int long_t = n_long > 0 ? long_row_threshold : INT32_MAX;
+    const int nch = n_long > 0 ? n_chunks : 0;
+    int32_t* tickets = n_long > 0 ? long_tickets : nullptr;
+#define MMREC_SPMM_CASE(D)                                                                                          \
+    case D:                                                                                                         \
+        launch_spmm_masked<D>(s, blocks, nch, rowptr, colidx, vals, keep_bits, val_scale, X, ep, n_rows, long_t,    \
+                              rows_per_group, long_rows, long_chunk_ptr, n_long, partials, tickets);                \
+        break;
+    switch (d / MMREC_EMB_DIM) {
+        MMREC_SPMM_CASE(1) MMREC_SPMM_CASE(2) MMREC_SPMM_CASE(3) MMREC_SPMM_CASE(4) MMREC_SPMM_CASE(5)
+        MMREC_SPMM_CASE(6)
+    }
+#undef MMREC_SPMM_CASE
+    MMREC_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int mmrec_edge_keep_bits(const uint8_t* keep, int64_t n_edges, const int64_t* perm_a, uint32_t* bits_a,
+                                    const int64_t* perm_b, uint32_t* bits_b, mmrec_stream_t stream) {
+    if (n_edges < 0 || n_edges > (int64_t)INT32_MAX) return MMREC_ERR_BAD_ARG;  // CSR positions are int32
+    if (n_edges == 0) return 0;
+    if (!keep || !bits_a || (perm_b && !bits_b)) return MMREC_ERR_BAD_ARG;
+    if ((const void*)bits_a == (const void*)keep || (const void*)bits_b == (const void*)keep || bits_a == bits_b)
+        return MMREC_ERR_BAD_ARG;
+    const int64_t n_pos = ((n_edges + 31) >> 5) << 5;  // whole words
+    hipLaunchKernelGGL(edge_keep_bits_kernel, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, mmrec_stream(stream),
+                       keep, (long long)n_edges, perm_a, bits_a, perm_b, bits_b);
     MMREC_RETURN_LAUNCH_STATUS();
 }
 

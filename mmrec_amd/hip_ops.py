@@ -1901,6 +1901,214 @@ def spmm_vals(dyn: DynGraph, X, vals):
 
 
 # ------------------------------------------------------------------------------------------------
+# Edge dropout inside the SpMM (common/encoders.py:77-103): fixed values, a fresh keep mask per call, one bit per entry
+# (mmrec_edge_keep_bits, mmrec_spmm_csr_masked_f32; additive to ABI 16)
+# ------------------------------------------------------------------------------------------------
+EDGE_DROPOUT = True   # False: both edge-dropout ops are the spmm_vals / stack().mean() composition (A/B runs)
+
+
+class EdgeDropoutGraph:
+    """A `DynGraph` with a FIXED value vector `vals` [E] (fp32, the DynGraph's edge order, no gradient) whose entries are
+    dropped per call by a keep mask.  The two permuted value copies (CSR order, transposed CSR order) are made here, once;
+    `dyn.fwd.vals` / `dyn.bwd.vals` are not touched, so the same DynGraph keeps serving `spmm_vals`."""
+
+    def __init__(self, dyn, vals):
+        if not isinstance(dyn, DynGraph):
+            raise _lib.MMRecHipError("EdgeDropoutGraph wants a DynGraph")
+        if not isinstance(vals, torch.Tensor) or vals.dtype != torch.float32 or vals.dim() != 1:
+            raise _lib.MMRecHipError("vals must be a 1-d float32 tensor")
+        if vals.numel() != dyn.rows.numel():
+            raise _lib.MMRecHipError("vals must have one value per edge of the DynGraph (%d), got %d" %
+                                     (dyn.rows.numel(), vals.numel()))
+        if vals.requires_grad:
+            raise _lib.MMRecHipError("vals must not require grad: the masked product is differentiable in X only "
+                                     "(learned values: spmm_vals)")
+        _chk(vals, torch.float32, "vals", 1)
+        self.dyn, self.vals, self.n_edges = dyn, vals, int(vals.numel())
+        self.vals_fwd = vals[dyn.perm].contiguous()
+        self.vals_bwd = vals[dyn.perm_t].contiguous()
+
+
+def _edge_dropout_check(eg, X, keep):
+    """the host checks of both ops, before any launch (shapes and types first, so that they speak without a device too)"""
+    if not isinstance(eg, EdgeDropoutGraph):
+        raise _lib.MMRecHipError("eg must be an EdgeDropoutGraph")
+    if eg.vals.requires_grad:
+        raise _lib.MMRecHipError("vals must not require grad")
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.dim() != 1:
+        raise _lib.MMRecHipError("keep must be a 1-d torch.bool tensor in edge order")
+    if keep.numel() != eg.n_edges:
+        raise _lib.MMRecHipError("keep must have one flag per edge (%d), got %d" % (eg.n_edges, keep.numel()))
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype != torch.float32:
+        raise _lib.MMRecHipError("X must be a 2-d float32 tensor")
+    if X.shape[0] < eg.dyn.n_cols:
+        raise _lib.MMRecHipError("X must have at least %d rows, got %d" % (eg.dyn.n_cols, X.shape[0]))
+    if not (X.is_cuda and keep.is_cuda and eg.vals.is_cuda):
+        raise _lib.MMRecHipError("X, keep and vals must be device tensors (the hot path has no CPU fallback)")
+
+
+def edge_dropout_served(eg, X):
+    """True where the edge-dropout ops run the masked kernels: the `EDGE_DROPOUT` switch on, X 64 k <= 384 wide (the feature
+    slices have no masked form) and the entry positions within int32.  Otherwise they run the composition of the older
+    kernels, `spmm_vals` on the zero-valued form."""
+    d = X.shape[1]
+    return bool(EDGE_DROPOUT and d > 0 and d % EMB_DIM == 0 and d <= 6 * EMB_DIM and eg.n_edges < 2 ** 31)
+
+
+def edge_keep_bits(keep, perm_a=None, perm_b=None, two=False):
+    """keep [E] (bool / uint8, edge order) -> packed int32 words, bit j = keep[perm[j]] (None: identity), for one order or
+    (`two`, or a `perm_b`) two in ONE launch; bits past E are zero.  Returns (bits_a, bits_b or None)."""
+    if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1:
+        raise _lib.MMRecHipError("keep must be a 1-d bool / uint8 tensor")
+    if not keep.is_cuda or not keep.is_contiguous():
+        raise _lib.MMRecHipError("keep must be a contiguous device tensor")
+    E = keep.numel()
+    for t, nm in ((perm_a, "perm_a"), (perm_b, "perm_b")):
+        if t is not None and _chk(t, torch.int64, nm, 1).numel() != E:
+            raise _lib.MMRecHipError("%s must have %d entries" % (nm, E))
+    two = two or perm_b is not None
+    lib = _lib.load()
+    words = torch.zeros(2 if two else 1, max((E + 31) // 32, 1), dtype=torch.int32, device=keep.device)
+    k8 = keep.view(torch.uint8)
+    _lib.check(lib.mmrec_edge_keep_bits(_p(k8), E, _p(perm_a), _p(words[0]), _p(perm_b), _p(words[1]) if two else None,
+                                        _stream()), "edge_keep_bits")
+    return words[0], (words[1] if two else None)
+
+
+def spmm_masked_raw(g: CsrGraph, vals, keep_bits, X, Y=None, Z=None, acc_in=None, acc_out=None, alpha=1.0, beta=1.0,
+                    acc_scale=1.0, val_scale=1.0, tickets=True):
+    """spmm_raw on the CSR of `g` with the values `vals` [nnz] (CSR order; g.vals is not read) and the entries whose bit of
+    `keep_bits` is clear removed.  `tickets=False`: the two-launch finish.  No autograd."""
+    lib = _lib.load()
+    _chk(X, torch.float32, "X", 2), _chk(vals, torch.float32, "vals", 1), _chk(keep_bits, torch.int32, "keep_bits", 1)
+    d = X.shape[1]
+    if d % EMB_DIM or d > 6 * EMB_DIM or X.shape[0] < g.n_cols:
+        raise _lib.MMRecHipError("X must be [>=%d, 64*k <= 384], got %s" % (g.n_cols, tuple(X.shape)))
+    if vals.numel() != g.nnz or keep_bits.numel() * 32 < g.nnz:
+        raise _lib.MMRecHipError("vals must be [%d] and keep_bits hold a bit for each" % g.nnz)
+    for t, nm in ((Y, "Y"), (Z, "Z"), (acc_in, "acc_in"), (acc_out, "acc_out")):
+        if t is not None:
+            _chk(t, torch.float32, nm, 2)
+            if t.shape[0] < g.n_rows or t.shape[1] != d:
+                raise _lib.MMRecHipError("%s must be [>=%d, %d]" % (nm, g.n_rows, d))
+    g.checked(lib.mmrec_spmm_csr_masked_f32(_p(g.rowptr), _p(g.colidx), _p(vals), _p(X), _p(Y), _p(Z), _p(acc_in),
+                                            _p(acc_out), g.n_rows, d, float(alpha), float(beta), float(acc_scale),
+                                            g.long_row_threshold, _p(g.long_rows), _p(g.long_chunk_ptr), g.n_long,
+                                            g.n_chunks, _p(g.partials_for(d)), _p(g.long_tickets) if tickets else None,
+                                            _p(keep_bits), float(val_scale), _stream()), "spmm_csr_masked_f32")
+    return Y if Y is not None else acc_out
+
+
+def _edge_dropout_values(eg, keep, scale):
+    """the zero-valued form of the masked matrix: what the composition feeds spmm_vals"""
+    return (eg.vals * keep.to(eg.vals.dtype)) * scale
+
+
+def _spmm_edge_dropout_composed(eg, X, keep, scale):
+    return spmm_vals(eg.dyn, X, _edge_dropout_values(eg, keep, scale))
+
+
+def _lightgcn_mean_edge_dropout_composed(eg, E0, n_layers, keep, scale):
+    vals = _edge_dropout_values(eg, keep, scale)
+    layers = [E0]
+    for _ in range(int(n_layers)):
+        E0 = spmm_vals(eg.dyn, E0, vals)
+        layers.append(E0)
+    return torch.stack(layers, dim=1).mean(dim=1)
+
+
+class _SpMMEdgeDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, eg, keep, scale):
+        dyn = eg.dyn
+        X = X.contiguous()
+        bits_f, bits_b = edge_keep_bits(keep, dyn.perm, dyn.perm_t)     # both orders, one launch
+        Y = torch.empty(dyn.n_rows, X.shape[1], dtype=torch.float32, device=X.device)
+        spmm_masked_raw(dyn.fwd, eg.vals_fwd, bits_f, X, Y=Y, val_scale=scale)
+        ctx.eg, ctx.scale, ctx.x_rows = eg, scale, X.shape[0]
+        ctx.save_for_backward(bits_b)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        bits_b, = ctx.saved_tensors
+        eg, dyn = ctx.eg, ctx.eg.dyn
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        dY = dY.contiguous()
+        # X may carry more rows than the graph has columns: they receive no gradient
+        alloc = torch.empty if ctx.x_rows == dyn.n_cols else torch.zeros
+        dX = alloc(ctx.x_rows, dY.shape[1], dtype=torch.float32, device=dY.device)
+        spmm_masked_raw(dyn.bwd, eg.vals_bwd, bits_b, dY, Y=dX, val_scale=ctx.scale)
+        return dX, None, None, None
+
+
+def spmm_edge_dropout(eg: EdgeDropoutGraph, X, keep, scale=1.0):
+    """(scale * (A o keep)) @ X, differentiable in X: A the fixed values of `eg`, keep a torch.bool [E] in edge order.  The
+    dropped entries are absent -- never gathered -- not zeros (sparse_dropout, encoders.py:92-103).  One pack launch for
+    both orders in the forward; the backward is one masked launch on the transposed side."""
+    _edge_dropout_check(eg, X, keep)
+    if not edge_dropout_served(eg, X):
+        return _spmm_edge_dropout_composed(eg, X, keep, scale)
+    return _SpMMEdgeDropout.apply(X, eg, keep, float(scale))
+
+
+class _LightGCNMeanEdgeDropout(torch.autograd.Function):
+    """_LightGCNMean on the masked matrix: L masked launches accumulating through the epilogue, Horner backward on the
+    transposed side, one pack per call"""
+
+    @staticmethod
+    def forward(ctx, E0, eg, n_layers, keep, scale):
+        ctx.eg, ctx.L, ctx.scale = eg, int(n_layers), scale
+        dyn, L = eg.dyn, int(n_layers)
+        E0 = E0.contiguous()
+        if L == 0:
+            return E0.clone()
+        bits_f, bits_b = edge_keep_bits(keep, dyn.perm, dyn.perm_t)
+        ctx.save_for_backward(bits_b)
+        acc = torch.empty_like(E0)
+        bufs = [torch.empty_like(E0) if L > 1 else None, torch.empty_like(E0) if L > 2 else None]
+        cur = E0
+        for layer in range(1, L + 1):
+            last = layer == L
+            Y = None if last else bufs[(layer - 1) % 2]
+            spmm_masked_raw(dyn.fwd, eg.vals_fwd, bits_f, cur, Y=Y, acc_in=E0 if layer == 1 else acc, acc_out=acc,
+                            acc_scale=1.0 / (L + 1) if last else 1.0, val_scale=scale)
+            cur = Y
+        return acc
+
+    @staticmethod
+    def backward(ctx, dOut):
+        L, eg = ctx.L, ctx.eg
+        dOut = dOut.contiguous()
+        if L == 0:
+            return dOut, None, None, None, None
+        bits_b, = ctx.saved_tensors
+        s = 1.0 / (L + 1)
+        bufs = [torch.empty_like(dOut), torch.empty_like(dOut) if L > 1 else None]
+        t = dOut
+        for j in range(L):  # t <- s*dOut + A^T t   (first step also scales the inner term)
+            out = bufs[j % 2]
+            spmm_masked_raw(eg.dyn.bwd, eg.vals_bwd, bits_b, t, Y=out, Z=dOut, alpha=s if j == 0 else 1.0, beta=s,
+                            val_scale=ctx.scale)
+            t = out
+        return t, None, None, None, None
+
+
+def lightgcn_mean_edge_dropout(eg: EdgeDropoutGraph, E0, n_layers, keep, scale=1.0):
+    """1/(L+1) * sum_{l=0..L} (scale * (A o keep))^l E0 on a square graph: the dropout branch of LightGCN_Encoder
+    (encoders.py:105-127) with the layer mean in the SpMM's accumulator epilogue, as `lightgcn_mean` has it."""
+    _edge_dropout_check(eg, E0, keep)
+    if eg.dyn.n_rows != eg.dyn.n_cols or E0.shape[0] != eg.dyn.n_rows:
+        raise _lib.MMRecHipError("lightgcn_mean_edge_dropout wants a square graph and E0 [n, d]")
+    if int(n_layers) < 0:
+        raise _lib.MMRecHipError("n_layers must be >= 0")
+    if not edge_dropout_served(eg, E0):
+        return _lightgcn_mean_edge_dropout_composed(eg, E0, n_layers, keep, scale)
+    return _LightGCNMeanEdgeDropout.apply(E0, eg, int(n_layers), keep, float(scale))
+
+
+# ------------------------------------------------------------------------------------------------
 # Per-edge dot products (SDDMM): the other half of the learned-values pattern (mmrec_edge_dot_*, ABI 16)
 # ------------------------------------------------------------------------------------------------
 EDGE_DOT = True       # False: every edge_dot call (and d vals of spmm_vals) is the gather-multiply-reduce composition (A/B runs)

@@ -112,8 +112,16 @@ def main():
     ap.add_argument("--two-step-projection", action="store_true", help="hip_gathered_projection False: FREEDOM / BM3 gather the batch's "
                                                                         "feature rows, then project the copy (A/B of hip_ops.linear_rows)")
     ap.add_argument("--fast-forward", action="store_true", help="lazy_adam_fast_forward: closed-form catch-up (opt-in, not bit-identical)")
+    ap.add_argument("--fused-edge-dropout", action="store_true", help="selfcf: fused_edge_dropout True (the encoder's sparse dropout "
+                                                                       "inside the SpMM, hip_ops.lightgcn_mean_edge_dropout)")
+    ap.add_argument("--edge-dropout-ab", type=int, metavar="RUNS", help="selfcf: RUNS runs with fused_edge_dropout on and RUNS with it "
+                                                                        "off, alternated in this process; ms per batch of each and its spread")
     args = ap.parse_args()
     cd = dict(device_neg_sampling=args.device_neg_sampling)
+    if args.fused_edge_dropout or args.edge_dropout_ab:
+        if args.config != "selfcf":
+            ap.error("fused_edge_dropout is a key of SELFCFED_LGN's encoder: use it with `selfcf`")
+        cd['fused_edge_dropout'] = True
     if args.graph_step or args.eager:
         cd['hip_graph_step'] = bool(args.graph_step)       # default: 'auto' (overall.yaml)
     if args.no_prefetch:
@@ -132,6 +140,17 @@ def main():
         cd['hip_linear_split'] = False
     if args.two_step_projection:
         cd['hip_gathered_projection'] = False
+    if args.edge_dropout_ab:
+        ms = {True: [], False: []}
+        for i in range(2 * args.edge_dropout_ab):
+            on = i % 2 == 0
+            ms[on].append(run("selfcf", dict(cd, fused_edge_dropout=on), args.epochs, verbose=False)["ms_per_batch"])
+            print("[selfcf] run %d fused_edge_dropout %s: %.3f ms/batch" % (i // 2, on, ms[on][-1]), flush=True)
+        for on in (True, False):
+            v = sorted(ms[on])
+            print("[selfcf] fused_edge_dropout %-5s ms/batch median %.3f min %.3f max %.3f (spread %.3f) over %d runs" % (
+                on, v[len(v) // 2], v[0], v[-1], v[-1] - v[0], len(v)), flush=True)
+        return
     if args.json:
         names = TIER if args.config == "tier" else [args.config]
         out = {n: run(n, cd, args.epochs) for n in names}

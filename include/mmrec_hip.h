@@ -722,7 +722,9 @@ int mmrec_adam_rows_step_f32(float* p, float* m, float* v, const int64_t* ids, i
  * backward ... mmrec_adam_prepare ... hist_set_dev ... rows_step_dev.  hist_set_dev does not write beyond `capacity`
  * entries: it raises *overflow (sticky, device int32) instead, which the host checks between epochs; from then on
  * catchup_dev / rows_step_dev (ABI 7: they take the same `capacity`) leave the rows untouched -- there is no table entry to
- * replay from -- so the run can be resumed from the state before the overflowing step. */
+ * replay from -- so the run can be resumed from the state before the overflowing step.  Such a refused call returns before
+ * it looks at a row, so the marks mmrec_adam_rows_owner made for it are NOT released: whoever resumes refills `owner` with
+ * INT_MAX first (LazyRowEmbedding.resume does).  hist[capacity - 1] is the last entry ever written. */
 int mmrec_adam_hist_set_dev(float* hist, int32_t capacity, const int64_t* step_dev, const float* hyper_dev,
                             int32_t* overflow, mmrec_stream_t stream);
 int mmrec_adam_rows_catchup_dev_f32(float* p, float* m, float* v, const int64_t* ids, int32_t* owner, int32_t n_ids,

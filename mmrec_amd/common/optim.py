@@ -5,7 +5,15 @@ tables are trainable; on the GPU torch's foreach path makes ~12 passes over them
 names (`step`, `exp_avg`, `exp_avg_sq`) as torch's, so LambdaLR and state_dict round-trips work.
 
 `capturable=True` keeps the step count and learning rate in device memory (one tiny prepare kernel per
-step derives the bias corrections), so a whole training step can be captured in a hipGraph and replayed."""
+step derives the bias corrections), so a whole training step can be captured in a hipGraph and replayed.
+
+Step counts.  `capturable=False`: every parameter follows its OWN count, as torch.optim.Adam does -- a parameter without
+`.grad` in some step is skipped and its bias corrections lag the others'.  `capturable=True`: a parameter group has ONE device
+counter, advanced once per `step()`, and every parameter updated in that step takes the GROUP's bias corrections, also one
+that was skipped earlier (torch's capturable Adam keeps a counter per parameter).  This is intended: a captured step cannot
+branch on which gradients exist, and every parameter of the models here receives a gradient in every step; the host mirror
+`state[p]['step']` counts the parameter's own updates only until `state_dict()` is called, which overwrites every
+parameter's `step` with the group's device count (the count a resumed run continues from).  tests/test_adam_fuzz_gpu.py pins both behaviours."""
 import ctypes
 
 import torch

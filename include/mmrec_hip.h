@@ -509,6 +509,33 @@ int mmrec_edge_attention_bwd_f32(const int32_t* rowptr, int32_t n_rows, const in
                                  const float* dAlpha, int32_t d, int64_t n_edges, float* ds, float* dQ, float* dKV,
                                  const float* dKV_base, mmrec_stream_t stream);
 
+/* Row-wise log-sum-exp of scale * Q K^T against a whole table, with gradients to both operands, never storing the [B, N]
+ * scores.  ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: exp(normalize(e[ids]) @ normalize(all).T / tau).sum(1) -- lgmrec.py:157-164 (the batch against every user / item)
+ *           and pgl.py:226-231 (two dropout views of the batch, width 128) -- and autograd's copies of that matrix.
+ *   lse[i] = log sum_{j<N} exp(scale <Q[i], K[j]>)            Q [B, d], K [N, d] fp32 row-major, d == 64 or 128, lse [B]
+ *   dQ[i]  = scale g[i] sum_j p_ij K[j]                       p_ij = exp(scale s_ij - lse[i]),  g [B] = dL / d lse
+ *   dK[j]  = scale sum_i g[i] p_ij Q[i]                       dQ [B, d], dK [N, d]: either may be NULL (not computed)
+ * Q == K is allowed (the caller adds dQ and dK); outputs must not alias inputs.  Scores are fp32 fma chains in natural k order
+ * on the fp32-input MFMA, recomputed in the backward: lse (the caller's) is the only state between the two calls.  Running
+ * maximum and rescaled sum per row: logits of any finite magnitude give a finite lse.  Grid: 128-row tiles x column splits of
+ * mmrec_score_lse_split_cols(B, N, 0) columns (a function of B and N alone; 0 for an empty K; mode 1 / 2: the columns of K per
+ * split of the dQ sweep / the rows of Q per split of the dK sweep, whose tiles are 128 rows of Q / of K); per-split results
+ * are combined in split order.  No atomics: two calls on the same inputs give the same bits, forward and gradients.
+ * N == 0: lse = -inf and zero gradients; B == 0: nothing to write but dK, which is zeroed.  A non-finite value in row i of Q
+ * may make lse[i] non-finite and leaves every other row's lse unchanged.
+ * workspace: mmrec_score_lse_workspace_bytes(B, N, d) bytes (16-byte aligned) serve either call: 2 * splits * B floats for the
+ * forward; for the backward the per-split partial gradients, at most 4 (B + N) d floats for each operand.
+ * d not 64 / 128 or a negative size: MMREC_ERR_BAD_ARG; B or N > 2^30: MMREC_ERR_UNSUPPORTED; a NULL Q / K / lse / g /
+ * workspace where it is needed, dQ and dK both NULL: MMREC_ERR_BAD_ARG -- before any launch.  No synchronisation, no
+ * allocation, no data-dependent launch shape, capture-safe, no global state. */
+int32_t mmrec_score_lse_split_cols(int32_t B, int32_t N, int32_t mode);
+size_t mmrec_score_lse_workspace_bytes(int32_t B, int32_t N, int32_t d);
+int mmrec_score_lse_f32(const float* Q, const float* K, int32_t B, int32_t N, int32_t d, float scale, float* lse,
+                        void* workspace, mmrec_stream_t stream);
+int mmrec_score_lse_bwd_f32(const float* Q, const float* K, int32_t B, int32_t N, int32_t d, float scale, const float* lse,
+                            const float* g, float* dQ, float* dK, void* workspace, mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

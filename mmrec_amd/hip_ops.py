@@ -2443,6 +2443,84 @@ def edge_attention(Q, KV, dyn, eps=1e-16, fused_backward=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# Contrastive log-sum-exp against a whole table (mmrec_score_lse_f32): lse[i] = log sum_j exp(scale <Q[i], K[j]>)
+# ------------------------------------------------------------------------------------------------
+SCORE_LSE_WIDTHS = (64, 128)
+
+
+def score_lse_split_cols(B, N, mode=0):
+    """columns of K one workgroup of the forward sweeps (the library's plan for the shape; 0 for an empty K); mode 1: the same
+    for the dQ sweep, mode 2: the rows of Q one workgroup of the dK sweep walks"""
+    return int(_lib.load().mmrec_score_lse_split_cols(int(B), int(N), int(mode)))
+
+
+def score_lse_served(Q, K):
+    """True where `score_lse` runs the kernel: device fp32 contiguous [B, d] and [N, d] with d 64 or 128.  `Q is K` is allowed."""
+    def table(t):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
+                t.shape[1] in SCORE_LSE_WIDTHS and t.is_contiguous() and t.shape[0] <= (1 << 30))
+    return bool(table(Q) and table(K) and Q.shape[1] == K.shape[1])
+
+
+class _ScoreLse(torch.autograd.Function):
+    """forward(Q, K or None for `Q is K`, scale) -> lse [B]"""
+
+    @staticmethod
+    def forward(ctx, Q, K, scale):
+        ctx.same = K is None
+        if ctx.same:
+            K = Q
+        lib = _lib.load()
+        B, N, d = Q.shape[0], K.shape[0], Q.shape[1]
+        lse = torch.empty(B, dtype=torch.float32, device=Q.device)
+        ws = _ws(lib.mmrec_score_lse_workspace_bytes(B, N, d), Q.device)
+        _lib.check(lib.mmrec_score_lse_f32(_p(Q), _p(K), B, N, d, scale, _p(lse), _p(ws), _stream()), "score_lse")
+        ctx.scale = scale
+        ctx.save_for_backward(Q, K, lse)
+        return lse
+
+    @staticmethod
+    def backward(ctx, g):
+        Q, K, lse = ctx.saved_tensors
+        same = ctx.same
+        want_q, want_k = ctx.needs_input_grad[0], (ctx.needs_input_grad[0] if same else ctx.needs_input_grad[1])
+        if not (want_q or want_k):
+            return None, None, None
+        lib = _lib.load()
+        B, N, d = Q.shape[0], K.shape[0], Q.shape[1]
+        g = g.contiguous()
+        dQ = torch.empty_like(Q) if want_q else None
+        dK = torch.empty_like(K) if want_k else None
+        if B and N:
+            ws = _ws(lib.mmrec_score_lse_workspace_bytes(B, N, d), Q.device)
+            _lib.check(lib.mmrec_score_lse_bwd_f32(_p(Q), _p(K), B, N, d, ctx.scale, _p(lse), _p(g), _p(dQ), _p(dK), _p(ws),
+                                                   _stream()), "score_lse_bwd")
+        else:
+            for t in (dQ, dK):
+                if t is not None:
+                    t.zero_()
+        if same:
+            return dQ + dK, None, None
+        return dQ, dK, None
+
+
+def score_lse(Q, K, scale=1.0):
+    """lse[i] = log sum_j exp(scale <Q[i], K[j]>) -> [B], with autograd to Q and K, never holding the [B, N] logits: the
+    contrastive denominator of LGMRec's hypergraph term (lgmrec.py:157-164, the batch against EVERY user / item) and of PGL's
+    two-view InfoNCE (pgl.py:226-231).  Served by the kernel (`score_lse_served`: device fp32 contiguous tables of width 64 or
+    128): fp32-MFMA scores with a running maximum (logits of any finite size give a finite result), 128-row tiles x column
+    splits combined in a fixed order; the backward recomputes the scores from Q, K and the saved lse -- dQ[i] = scale g[i]
+    sum_j p_ij K[j], dK[j] = scale sum_i g[i] p_ij Q[i], p = exp(scale s - lse) -- with both products on the MFMA.  No atomics:
+    the same bits every call, so `DETERMINISTIC` changes nothing.  `Q is K`: the two gradients are added.  An empty K gives
+    -inf and zero gradients, as torch.logsumexp does.
+    EVERY OTHER CASE (CPU tensors, other widths or dtypes, non-contiguous operands) is exactly
+    `torch.logsumexp(scale * (Q @ K.T), dim=1)` with stock autograd."""
+    if score_lse_served(Q, K):
+        return _ScoreLse.apply(Q, None if Q is K else K, float(scale))
+    return torch.logsumexp(scale * (Q @ K.T), dim=1)
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

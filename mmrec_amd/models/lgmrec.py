@@ -7,7 +7,9 @@ forward: CGE = fused LightGCN layer mean; MGE = modal projection X W on the fp32
          hyperedge assignment X V (F x 4: a skinny library GEMM), R (X V) on the SpMM (4 columns padded to a 64-float
          row), Gumbel-softmax and the 4-hyperedge HGNN products in torch (I x 4 and U x 4 operands)
 loss   : fused BPR + EmbLoss on the batch rows; the hypergraph contrastive term scores the batch against EVERY
-         user / item (B x N logits, lgmrec.py:157-164), not in-batch: torch matmul
+         user / item (B x N logits, lgmrec.py:157-164), not in-batch: torch matmul.  With the config key `fused_ssl: True`
+         (absent / False: that path, untouched) the term is `hip_ops.score_lse` -- the row-wise log-sum-exp on the fp32 MFMA
+         that never stores the B x N matrix, forward or backward -- minus the positive logit, on `hip_ops.row_normalize` rows
 eval   : fused score + mask + top-K.  The reference draws fresh Gumbel noise in every forward, i.e. once per
          evaluation batch (lgmrec.py:196-200); here once per evaluate (the propagation is cached across batches).
 """
@@ -53,6 +55,7 @@ class LGMRec(FusedEvalMixin, GeneralRecommender):
         self.cl_weight = config['cl_weight']
         self.reg_weight = config['reg_weight']
         self.tau = 0.2
+        self.fused_ssl = bool(config['fused_ssl']) if 'fused_ssl' in config else False    # new key, default off
         self.n_nodes = self.n_users + self.n_items
         self.hgnnLayer = HGNNLayer(self.n_hyper_layer)
 
@@ -115,6 +118,9 @@ class LGMRec(FusedEvalMixin, GeneralRecommender):
         return u, i
 
     def ssl_triple_loss(self, emb1, emb2, all_emb):
+        if self.fused_ssl:      # -log(pos / ttl) = log ttl - <n1, n2> / tau, the B x N logits never stored
+            n1, n2, na = (hip_ops.row_normalize(x.contiguous()) for x in (emb1, emb2, all_emb))
+            return (hip_ops.score_lse(n1, na, 1.0 / self.tau) - torch.mul(n1, n2).sum(dim=1) / self.tau).sum()
         n1, n2, na = F.normalize(emb1), F.normalize(emb2), F.normalize(all_emb)
         pos_score = torch.exp(torch.mul(n1, n2).sum(dim=1) / self.tau)
         ttl_score = torch.exp(torch.matmul(n1, na.T) / self.tau).sum(dim=1)

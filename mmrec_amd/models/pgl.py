@@ -9,7 +9,9 @@ forward: both modal projections on the fp32 MFMA GEMM feed the graph (pgl.py:188
          and the fused BPR all run at row width 128
 loss   : fused BPR + reg_weight * mean of two InfoNCE terms between two dropout views of the batch rows
          (pgl.py:233-250; `reg_weight` is 0 in the reference's PGL.yaml -- the term is then skipped, it
-         contributes exactly zero loss and zero gradient)
+         contributes exactly zero loss and zero gradient).  With the config key `fused_ssl: True` (absent / False: the
+         torch path, untouched) each term is `hip_ops.score_lse` at width 128 minus the positive logit: no B x B matrix;
+         the dropout draws stay where they are, so a seeded run consumes the generator identically either way
 eval   : fused score + mask + top-K at row width 128
 mode 'global' needs `sparsesvd` (third-party, absent from the reference tree and this image): not built.
 """
@@ -89,6 +91,7 @@ class PGL(FusedEvalMixin, GeneralRecommender):
         self.reg_weight = config['reg_weight']
         self.mm_image_weight = config['mm_image_weight']
         self.dropout = config['dropout']
+        self.fused_ssl = bool(config['fused_ssl']) if 'fused_ssl' in config else False    # new key, default off
         self.n_nodes = self.n_users + self.n_items
 
         self.interaction_matrix = dataset.inter_matrix(form='coo').astype(np.float32)
@@ -149,6 +152,13 @@ class PGL(FusedEvalMixin, GeneralRecommender):
         ttl_score = torch.exp(torch.matmul(view1, view2.transpose(0, 1)) / temperature).sum(dim=1)
         return torch.mean(-torch.log(pos_score / ttl_score))
 
+    @staticmethod
+    def InfoNCE_fused(view1, view2, temperature):
+        """the same loss as `InfoNCE`: -log(pos / ttl) = log ttl - <v1, v2> / T, the log-sum-exp in one kernel"""
+        view1, view2 = hip_ops.row_normalize(view1.contiguous()), hip_ops.row_normalize(view2.contiguous())
+        lse = hip_ops.score_lse(view1, view2, 1.0 / temperature)
+        return torch.mean(lse - (view1 * view2).sum(dim=-1) / temperature)
+
     def calculate_loss(self, interaction):
         users, pos_items = interaction[0], interaction[1]
         ua, ia = self.forward(self.sub_graph)
@@ -162,5 +172,6 @@ class PGL(FusedEvalMixin, GeneralRecommender):
             return loss
         u_g, p_g = ua[users], ia[pos_items]
         drop = lambda x: F.dropout(x, self.dropout, self.training)
-        cl_loss = (self.InfoNCE(drop(u_g), drop(u_g), 0.2) + self.InfoNCE(drop(p_g), drop(p_g), 0.2)) / 2
+        nce = self.InfoNCE_fused if self.fused_ssl else self.InfoNCE
+        cl_loss = (nce(drop(u_g), drop(u_g), 0.2) + nce(drop(p_g), drop(p_g), 0.2)) / 2
         return loss + self.reg_weight * cl_loss

@@ -33,6 +33,7 @@ CONFIGS = {
                                 "dropout_rate": 0.1}),
     "selfcf": ("SELFCFED_LGN", "baby", {"n_layers": 2, "dropout": 0.2, "reg_weight": 1e-3}),
     "pgl": ("PGL", "baby", {"dropout": 0.2, "reg_weight": 0, "mode": "local"}),
+    "pgl_cl": ("PGL", "baby", {"dropout": 0.2, "reg_weight": 1e-2, "mode": "local"}),      # the contrastive term switched on
     "bpr": ("BPR", "baby", {"reg_weight": 1e-2}),
     "mmgcf": ("MMGCF", "baby", {"n_ui_layers": 2, "reg_weight": 1e-3, "fusion_mode": "mean", "weighting": "equal",
                                 "dropout": 0.5}),
@@ -116,8 +117,16 @@ def main():
                                                                        "inside the SpMM, hip_ops.lightgcn_mean_edge_dropout)")
     ap.add_argument("--edge-dropout-ab", type=int, metavar="RUNS", help="selfcf: RUNS runs with fused_edge_dropout on and RUNS with it "
                                                                         "off, alternated in this process; ms per batch of each and its spread")
+    ap.add_argument("--fused-ssl", action="store_true", help="lgmrec / pgl_cl: fused_ssl True (the contrastive log-sum-exp in "
+                                                             "hip_ops.score_lse instead of the B x N torch matrix)")
+    ap.add_argument("--fused-ssl-ab", type=int, metavar="RUNS", help="lgmrec / pgl_cl: RUNS runs with fused_ssl on and RUNS with it off, "
+                                                                     "alternated in this process; ms per batch of each and its spread")
     args = ap.parse_args()
     cd = dict(device_neg_sampling=args.device_neg_sampling)
+    if args.fused_ssl or args.fused_ssl_ab:
+        if args.config not in ("lgmrec", "pgl", "pgl_cl"):
+            ap.error("fused_ssl is a key of LGMRec and PGL: use it with `lgmrec` or `pgl_cl` (`pgl` has the term's weight at 0)")
+        cd['fused_ssl'] = True
     if args.fused_edge_dropout or args.edge_dropout_ab:
         if args.config != "selfcf":
             ap.error("fused_edge_dropout is a key of SELFCFED_LGN's encoder: use it with `selfcf`")
@@ -150,6 +159,17 @@ def main():
             v = sorted(ms[on])
             print("[selfcf] fused_edge_dropout %-5s ms/batch median %.3f min %.3f max %.3f (spread %.3f) over %d runs" % (
                 on, v[len(v) // 2], v[0], v[-1], v[-1] - v[0], len(v)), flush=True)
+        return
+    if args.fused_ssl_ab:
+        ms = {True: [], False: []}
+        for i in range(2 * args.fused_ssl_ab):
+            on = i % 2 == 0
+            ms[on].append(run(args.config, dict(cd, fused_ssl=on), args.epochs, verbose=False)["ms_per_batch"])
+            print("[%s] run %d fused_ssl %s: %.3f ms/batch" % (args.config, i // 2, on, ms[on][-1]), flush=True)
+        for on in (True, False):
+            v = sorted(ms[on])
+            print("[%s] fused_ssl %-5s ms/batch median %.3f min %.3f max %.3f (spread %.3f) over %d runs" % (
+                args.config, on, v[len(v) // 2], v[0], v[-1], v[-1] - v[0], len(v)), flush=True)
         return
     if args.json:
         names = TIER if args.config == "tier" else [args.config]

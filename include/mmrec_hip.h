@@ -509,6 +509,47 @@ int mmrec_edge_attention_bwd_f32(const int32_t* rowptr, int32_t n_rows, const in
                                  const float* dAlpha, int32_t d, int64_t n_edges, float* ds, float* dQ, float* dKV,
                                  const float* dKV_base, mmrec_stream_t stream);
 
+/* Max over a node's neighbours with the argmax, and its backward: PyG's `aggr='max'` without the [n_edges, 64] message tensor.
+ * ADDITIVE to ABI 16: three new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: Base_gcn(aggr='max').propagate -- dualgnn.py:318-345, dragon.py:387-410 (x[src] gathered per edge, scatter-max at
+ *           the targets, and autograd's copies of both).
+ * Rows are the rows of a CSR (rowptr [n_rows + 1], colidx [n_edges], device, int32); slot j of row r lives at position
+ * p = perm ? perm[j] : j of the caller's edge list (perm as for mmrec_segment_softmax_f32).  X [n_x, 64] fp32 row-major.
+ *   Y[r][c]   = max over the slots j of row r of X[colidx[j]][c]                     Y [n_rows, 64] fp32
+ *   arg[r][c] = the position p of the slot chosen                                    arg [n_rows, 64] int32
+ * SELECTION RULE (part of the contract), per (r, c): the chosen slot is the first in CSR order whose value is NaN; without a
+ * NaN it is the first in CSR order that attains the maximum under IEEE `>` (-0 and +0 are tied: the first wins).  Y holds the
+ * chosen value's bits (the forward is exact).  A row without (present) entries: Y = 0 and arg = -1.  EVERY row of Y and of arg
+ * is written.  A colidx outside [0, n_x) or a position outside [0, n_edges) is an absent edge: never an address, never chosen.
+ * Rows of at most mmrec_neighbor_max_group_max() entries: one 16-lane group per row; longer rows: one workgroup per row of
+ * long_rows [n_long] (device, int32; listed as for mmrec_edge_attention_f32 -- the constant equals
+ * mmrec_segment_softmax_group_max(), so one list serves all three); n_long == 0: the groups serve every row.  A list that names
+ * other rows leaves rows unwritten (hip_ops checks it on the host).  The result does not depend on the launch shape: partial
+ * states are combined by (is NaN, value, CSR slot).  No atomics.  Y and arg must not alias an input.
+ * d != 64: MMREC_ERR_UNSUPPORTED; negative sizes: MMREC_ERR_BAD_ARG; n_rows == 0: 0 and no launch; n_edges or n_x > 2^31 - 1:
+ * MMREC_ERR_UNSUPPORTED; a NULL rowptr / Y / arg, n_edges > 0 with a NULL colidx / X, n_long > 0 with NULL long_rows:
+ * MMREC_ERR_BAD_ARG -- in this order, before any launch (n_edges == 0 with rows: Y = 0 and arg = -1 ARE written).
+ *
+ * mmrec_neighbor_max_bwd_f32: a pull over the TRANSPOSED CSR of the same edge list -- rowptr_t [n_cols + 1], rowidx_t
+ * [n_edges] (the row of each slot), perm_t (NULL = identity), long_cols [n_long_t] listed as long_rows is:
+ *   dX[s][c] = dX_base[s][c] + sum of dY[r][c] over the slots jt of column s with arg[r][c] == p,
+ *              r = rowidx_t[jt], p = perm_t ? perm_t[jt] : jt                        dX, dX_base [n_cols, 64], dY [n_rows, 64]
+ * dX_base may be NULL; it must not be dX.  The comparison is on positions: of duplicate (r, s) edges only the chosen copy
+ * contributes.  Terms are added in slot order by the 16-lane group that owns the column; a listed column's 16 partial sums are
+ * added after the base in a fixed order: no atomics, the same bits every call.  EVERY row of dX is written.  An r outside
+ * [0, n_rows) or a position outside [0, n_edges) is an absent edge: never an address, adds nothing.
+ * d != 64: MMREC_ERR_UNSUPPORTED; negative sizes: MMREC_ERR_BAD_ARG; n_cols == 0: 0 and no launch; n_edges or n_rows > 2^31 - 1:
+ * MMREC_ERR_UNSUPPORTED; a NULL rowptr_t / dX, dX_base == dX, n_edges > 0 with a NULL rowidx_t / arg / dY, n_long_t > 0 with
+ * NULL long_cols: MMREC_ERR_BAD_ARG -- in this order, before any launch.
+ * All three: no synchronisation, no allocation, capture-safe, no global state. */
+int32_t mmrec_neighbor_max_group_max(void);
+int mmrec_neighbor_max_f32(const int32_t* rowptr, int32_t n_rows, const int32_t* colidx, const int64_t* perm,
+                           const int32_t* long_rows, int32_t n_long, const float* X, int64_t n_x, int32_t d, int64_t n_edges,
+                           float* Y, int32_t* arg, mmrec_stream_t stream);
+int mmrec_neighbor_max_bwd_f32(const int32_t* rowptr_t, int32_t n_cols, const int32_t* rowidx_t, const int64_t* perm_t,
+                               const int32_t* long_cols, int32_t n_long_t, const int32_t* arg, int64_t n_rows, const float* dY,
+                               int32_t d, int64_t n_edges, float* dX, const float* dX_base, mmrec_stream_t stream);
+
 /* Row-wise log-sum-exp of scale * Q K^T against a whole table, with gradients to both operands, never storing the [B, N]
  * scores.  ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
  * replaces: exp(normalize(e[ids]) @ normalize(all).T / tau).sum(1) -- lgmrec.py:157-164 (the batch against every user / item)

@@ -76,6 +76,9 @@ SIGNATURES = {
                                            _P, _P, _P]),
     "mmrec_edge_attention_bwd_f32": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, _P, _P, _P, _P, c_int32, _P, c_int64, _P, c_int64,
                                                _P, _P, _P, _P, c_int32, c_int64, _P, _P, _P, _P, _P]),
+    "mmrec_neighbor_max_group_max": (c_int32, []),
+    "mmrec_neighbor_max_f32": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, _P, c_int64, c_int32, c_int64, _P, _P, _P]),
+    "mmrec_neighbor_max_bwd_f32": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, _P, c_int64, _P, c_int32, c_int64, _P, _P, _P]),
     "mmrec_score_lse_split_cols": (c_int32, [c_int32, c_int32, c_int32]),
     "mmrec_score_lse_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mmrec_score_lse_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P]),

@@ -2443,6 +2443,111 @@ def edge_attention(Q, KV, dyn, eps=1e-16, fused_backward=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# Max over a node's neighbours (mmrec_neighbor_max_f32): PyG's aggr='max' without the [n_edges, 64] message tensor
+# ------------------------------------------------------------------------------------------------
+NEIGHBOR_MAX = True   # False: every neighbor_max call is `neighbor_max_torch` (A/B runs)
+
+
+def neighbor_max_group_max():
+    """rows longer than this go to one workgroup each (the library's constant; equal to `segment_softmax_group_max()`)"""
+    return int(_lib.load().mmrec_neighbor_max_group_max())
+
+
+def _neighbor_max_side(dyn, by):
+    """`_softmax_side` for this op: its threshold is the softmax's, so it is the softmax's cached list; a library in which the
+    two constants differ is refused rather than served a list cut at the wrong length."""
+    if neighbor_max_group_max() != segment_softmax_group_max():
+        raise _lib.MMRecHipError("neighbor max: group maximum %d is not the segment softmax's %d"
+                                 % (neighbor_max_group_max(), segment_softmax_group_max()))
+    return _softmax_side(dyn, by)
+
+
+def neighbor_max_torch(X, rows, cols, n_rows):
+    """Y[r][c] = max over the edges e with rows[e] == r of X[cols[e]][c], and arg [n_rows, d] (int32) = the edge chosen, by the
+    kernel's SELECTION RULE: the first edge (lowest position among the row's edges) whose value is NaN; without a NaN the
+    first that attains the maximum (-0 and +0 tied); a row without edges: Y = 0, arg = -1.  Stock autograd: an explicit
+    first-maximal-edge argmin over positions, then ONE gather of X at the chosen (source, column) pairs, so the whole
+    gradient of Y[r][c] goes to the chosen edge's source -- not `scatter_reduce('amax')`'s even split among ties.  This is
+    the composition `neighbor_max` falls back to; its temporaries are [n_edges, d]."""
+    ne, d = rows.numel(), X.shape[1]
+    if ne == 0:
+        return X.new_zeros(n_rows, d), torch.full((n_rows, d), -1, dtype=torch.int32, device=X.device)
+    with torch.no_grad():
+        msg = X.detach()[cols]
+        isn = msg.isnan()
+        idx = rows.unsqueeze(1).expand(ne, d)
+        top = torch.full((n_rows, d), float('-inf'), dtype=X.dtype, device=X.device)
+        top = top.scatter_reduce(0, idx, torch.where(isn, torch.full_like(msg, float('inf')), msg), 'amax', include_self=True)
+        has_nan = torch.zeros(n_rows, d, dtype=torch.int32, device=X.device).scatter_reduce(0, idx, isn.to(torch.int32), 'amax')
+        cand = torch.where(has_nan[rows] > 0, isn, ~isn & (msg == top[rows]))
+        pos = torch.arange(ne, device=X.device).unsqueeze(1).expand(ne, d)
+        first = torch.full((n_rows, d), ne, dtype=torch.int64, device=X.device)
+        first = first.scatter_reduce(0, idx, torch.where(cand, pos, torch.full_like(pos, ne)), 'amin', include_self=True)
+        some = first < ne
+        src = cols[first.clamp(max=ne - 1)]
+        column = torch.arange(d, device=X.device).unsqueeze(0).expand(n_rows, d)
+    Y = torch.where(some, X[src, column], torch.zeros((), dtype=X.dtype, device=X.device))
+    return Y, torch.where(some, first, torch.full_like(first, -1)).to(torch.int32)
+
+
+def neighbor_max_served(X, dyn):
+    """True where `neighbor_max` runs the kernels: a device fp32 contiguous [dyn.n_cols, 64] table over a `DynGraph` that
+    holds both CSR forms, and the `NEIGHBOR_MAX` switch on."""
+    return bool(NEIGHBOR_MAX and isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and
+                X.shape[1] == EMB_DIM and X.is_contiguous() and X.shape[0] == dyn.n_cols and hasattr(dyn, "fwd"))
+
+
+class _NeighborMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, dyn):
+        g, perm, long_rows = _neighbor_max_side(dyn, "row")
+        _neighbor_max_side(dyn, "col")                          # the column side's list: host work, so here and not in backward
+        n_edges = dyn.rows.numel()
+        Y = torch.empty(dyn.n_rows, EMB_DIM, dtype=torch.float32, device=X.device)
+        arg = torch.empty(dyn.n_rows, EMB_DIM, dtype=torch.int32, device=X.device)
+        _lib.check(_lib.load().mmrec_neighbor_max_f32(_p(g.rowptr), g.n_rows, _p(g.colidx), _p(perm), _p(long_rows),
+                                                      0 if long_rows is None else long_rows.numel(), _p(X), X.shape[0], EMB_DIM,
+                                                      n_edges, _p(Y), _p(arg), _stream()), "neighbor_max")
+        ctx.dyn = dyn
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(arg)
+        ctx.save_for_backward(arg)
+        return Y, arg
+
+    @staticmethod
+    def backward(ctx, dY, _):
+        if dY is None or not ctx.needs_input_grad[0]:
+            return None, None
+        (arg,) = ctx.saved_tensors
+        dyn = ctx.dyn
+        g, perm_t, long_cols = _neighbor_max_side(dyn, "col")   # (cached since the forward)
+        dY = dY.contiguous()
+        dX = torch.empty(dyn.n_cols, EMB_DIM, dtype=torch.float32, device=dY.device)
+        _lib.check(_lib.load().mmrec_neighbor_max_bwd_f32(_p(g.rowptr), g.n_rows, _p(g.colidx), _p(perm_t), _p(long_cols),
+                                                          0 if long_cols is None else long_cols.numel(), _p(arg), dyn.n_rows,
+                                                          _p(dY), EMB_DIM, dyn.rows.numel(), _p(dX), None, _stream()),
+                   "neighbor_max_bwd")
+        return dX, None
+
+
+def neighbor_max(X, dyn):
+    """Max over the neighbours of every row of `dyn` (PyG's `aggr='max'`, Base_gcn of dualgnn.py:318-345 / dragon.py:387-410):
+    -> (Y [n_rows, d], arg [n_rows, d] int32) with Y[r][c] = max over the edges e = (r, col) of X[col][c] and arg[r][c] the
+    position in dyn's edge list of the edge chosen -- the first NaN of the row's edges, else the first that attains the
+    maximum (-0 = +0); a row without edges: Y = 0, arg = -1.  Differentiable in X (the whole gradient of Y[r][c] goes to the
+    chosen edge's source); `arg` is not differentiable.
+    Served by the kernels (`neighbor_max_served`): one launch (+ one for the rows longer than `neighbor_max_group_max()`)
+    forward over dyn.fwd / dyn.perm, one (+ one) backward -- a pull over dyn.bwd / dyn.perm_t that adds dY[r][c] where arg[r][c]
+    names the slot; no [n_edges, d] tensor in either direction, no atomics: both directions repeat bit for bit.  Both long lists
+    are built on the host at the first call on a DynGraph: call once before capturing a step.
+    EVERY OTHER CASE (CPU tensors, other widths or dtypes, non-contiguous tables, a graph object that holds only rows / cols,
+    the switch off) is `neighbor_max_torch` with stock autograd: the same rule, so the same Y bits and the same arg."""
+    if neighbor_max_served(X, dyn):
+        return _NeighborMax.apply(X, dyn)
+    return neighbor_max_torch(X, dyn.rows, dyn.cols, dyn.n_rows)
+
+
+# ------------------------------------------------------------------------------------------------
 # Contrastive log-sum-exp against a whole table (mmrec_score_lse_f32): lse[i] = log sum_j exp(scale <Q[i], K[j]>)
 # ------------------------------------------------------------------------------------------------
 SCORE_LSE_WIDTHS = (64, 128)

@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from mmrec_amd import hip_ops
 from mmrec_amd.models._base import FusedEvalMixin, GeneralRecommender
-from mmrec_amd.models.dualgnn import GCN, UserGraphMixin, np_xavier_normal, sym_norm_graph
+from mmrec_amd.models.dualgnn import GCN, UserGraphMixin, aggr_graph, check_aggr_mode, np_xavier_normal
 from mmrec_amd.models.freedom import load_or_build_mm_adj
 
 
@@ -31,9 +31,7 @@ class DRAGON(UserGraphMixin, FusedEvalMixin, GeneralRecommender):
         self.n_layers = config['n_mm_layers']
         self.knn_k = config['knn_k']
         self.mm_image_weight = config['mm_image_weight']
-        self.aggr_mode = config['aggr_mode']
-        if self.aggr_mode != 'add':
-            raise NotImplementedError("DRAGON: aggr_mode %r (the shipped config uses 'add')" % (self.aggr_mode,))
+        self.aggr_mode = check_aggr_mode(config['aggr_mode'], "DRAGON")
         self.construction = 'cat'
         self.reg_weight = config['reg_weight']
         self.drop_rate = 0.1
@@ -50,7 +48,7 @@ class DRAGON(UserGraphMixin, FusedEvalMixin, GeneralRecommender):
         self.mm_adj = load_or_build_mm_adj(config, self.v_feat, self.t_feat, self.knn_k, self.mm_image_weight,
                                            self.n_items, self.device, cache_name='mm_adj_{}.pt'.format(self.knn_k))
         inter = dataset.inter_matrix(form='coo').astype(np.float32)
-        self.graph = sym_norm_graph(inter, self.n_users, self.n_items, self.device)
+        self.graph = aggr_graph(self.aggr_mode, inter, self.n_users, self.n_items, self.device, "DRAGON")
         self.weight_u = nn.Parameter(np_xavier_normal(self.n_users, 2, 1))
         self.weight_u.data = F.softmax(self.weight_u.data, dim=1)
         self.weight_i = nn.Parameter(np_xavier_normal(self.n_items, 2, 1))
@@ -59,9 +57,9 @@ class DRAGON(UserGraphMixin, FusedEvalMixin, GeneralRecommender):
         self.MLP_user = nn.Linear(self.dim_latent * 2, self.dim_latent)
         self.v_preference = self.t_preference = None
         if self.v_feat is not None:
-            self.v_gcn = GCN(self.n_users, self.v_feat.size(1), self.dim_latent)
+            self.v_gcn = GCN(self.n_users, self.v_feat.size(1), self.dim_latent, self.aggr_mode)
         if self.t_feat is not None:
-            self.t_gcn = GCN(self.n_users, self.t_feat.size(1), self.dim_latent)
+            self.t_gcn = GCN(self.n_users, self.t_feat.size(1), self.dim_latent, self.aggr_mode)
         self.result_embed = nn.init.xavier_normal_(
             torch.tensor(np.random.randn(self.n_users + self.n_items, dim_x))).float().to(self.device)
 

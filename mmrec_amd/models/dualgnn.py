@@ -2,7 +2,8 @@
 
 Per modality: features -> MLP (F -> 256 -> 64, fp32 MFMA projection kernels) -> row-normalise together with a
 trainable user preference table -> two hops of D^-1/2 A D^-1/2 over the user-item graph, x + A x + A^2 x (PyG
-`Base_gcn(aggr='add')` twice; here the fused layer-accumulating CSR SpMM).  The user side is then smoothed over a
+`Base_gcn(aggr='add')` twice; here the fused layer-accumulating CSR SpMM).  `aggr_mode: 'mean'` is the same SpMM with
+1 / in-degree values on raw messages, `'max'` two calls of the neighbour-max kernel (`hip_ops.neighbor_max`).  The user side is then smoothed over a
 user-user co-occurrence graph: every user averages (softmax-of-count weights) the representations of k = 40
 neighbours -- the reference gathers a [U, 40, 64] tensor and batch-multiplies it; that is an SpMM with a [U, U]
 CSR of 40 entries per row, and its backward the SpMM with the transposed CSR.
@@ -45,6 +46,45 @@ def sym_norm_graph(inter_coo, n_users, n_items, device):
     return hip_ops.CsrGraph.from_coo_host(np.stack([dst, src]), val, n, n, device, symmetric=True)
 
 
+AGGR_MODES = ('add', 'mean', 'max')
+
+
+def mean_graph(inter_coo, n_users, n_items, device):
+    """the same cat(edges, flipped edges) list with values 1 / in-degree of the target (PyG `aggr='mean'` on raw messages,
+    Base_gcn.message returns x_j as it is); not symmetric: the transpose is built once, here"""
+    u = inter_coo.row.astype(np.int64)
+    i = inter_coo.col.astype(np.int64) + n_users
+    src, dst = np.concatenate([u, i]), np.concatenate([i, u])
+    n = n_users + n_items
+    deg = np.bincount(dst, minlength=n).astype(np.float32)
+    g = hip_ops.CsrGraph.from_coo_host(np.stack([dst, src]), (np.float32(1.0) / deg[dst]).astype(np.float32), n, n, device)
+    g.transpose()
+    return g
+
+
+def max_graph(inter_coo, n_users, n_items, device):
+    """the structure of the same list, targets as rows, for `hip_ops.neighbor_max` (PyG `aggr='max'` on raw messages): both
+    CSR forms and their permutations, built once"""
+    u = torch.from_numpy(inter_coo.row.astype(np.int64))
+    i = torch.from_numpy(inter_coo.col.astype(np.int64)) + n_users
+    src, dst = torch.cat([u, i]).to(device), torch.cat([i, u]).to(device)
+    n = n_users + n_items
+    return hip_ops.DynGraph(dst, src, n, n)
+
+
+def check_aggr_mode(aggr_mode, who):
+    if aggr_mode not in AGGR_MODES:
+        raise ValueError("%s: aggr_mode %r is not one of 'add', 'mean', 'max'" % (who, aggr_mode))
+    return aggr_mode
+
+
+def aggr_graph(aggr_mode, inter_coo, n_users, n_items, device, who):
+    """the user-item graph in the form Base_gcn's aggregation wants (dualgnn.py:318-345, dragon.py:387-410)"""
+    check_aggr_mode(aggr_mode, who)
+    build = {'add': sym_norm_graph, 'mean': mean_graph, 'max': max_graph}[aggr_mode]
+    return build(inter_coo, n_users, n_items, device)
+
+
 def np_xavier_normal(*shape):
     """nn.init.xavier_normal_(torch.tensor(np.random.randn(*shape), dtype=float32)): the numpy draw is
     overwritten, but it advances the global numpy stream the epoch shuffles read from"""
@@ -52,10 +92,13 @@ def np_xavier_normal(*shape):
 
 
 class GCN(nn.Module):
-    """reference GCN(dim_latent=64): preference table + 2-layer MLP, x + A x + A A x"""
+    """reference GCN(dim_latent=64): preference table + 2-layer MLP, x + A x + A A x; `aggr_mode` is Base_gcn's aggregation
+    and decides what `graph` is (`aggr_graph`): 'add' the D^-1/2 A D^-1/2 CSR, 'mean' the 1 / in-degree CSR, 'max' a DynGraph"""
 
-    def __init__(self, num_user, dim_feat, dim_latent):
+    def __init__(self, num_user, dim_feat, dim_latent, aggr_mode='add'):
         super().__init__()
+        self.aggr_mode = check_aggr_mode(aggr_mode, "GCN")
+        self.last_arg = None         # 'max': the (detached) argmax of the two hops of the last forward, for tests and debugging
         self.preference = nn.Parameter(np_xavier_normal(num_user, dim_latent))
         self.MLP = nn.Linear(dim_feat, 4 * dim_latent)
         self.MLP_1 = nn.Linear(4 * dim_latent, dim_latent)
@@ -63,6 +106,11 @@ class GCN(nn.Module):
     def forward(self, graph, features):
         temp = _lin64(self.MLP_1, F.leaky_relu(_lin64(self.MLP, features)))
         x = F.normalize(torch.cat((self.preference, temp), dim=0))
+        if self.aggr_mode == 'max':
+            h, a1 = hip_ops.neighbor_max(x, graph)
+            h_1, a2 = hip_ops.neighbor_max(h, graph)
+            self.last_arg = (a1.detach(), a2.detach())
+            return h + x + h_1, self.preference
         return hip_ops.lightgcn_mean(graph, x, 2) * 3.0, self.preference     # h + x + h_1
 
 
@@ -142,9 +190,7 @@ class DualGNN(UserGraphMixin, FusedEvalMixin, GeneralRecommender):
         super().__init__(config, dataset)
         dim_x = config['embedding_size']
         self.num_user, self.num_item = self.n_users, self.n_items
-        self.aggr_mode = config['aggr_mode']
-        if self.aggr_mode != 'add':
-            raise NotImplementedError("DualGNN: aggr_mode %r (the shipped config uses 'add')" % (self.aggr_mode,))
+        self.aggr_mode = check_aggr_mode(config['aggr_mode'], "DualGNN")
         self.construction = 'weighted_sum'
         self.reg_weight = config['reg_weight']
         self.drop_rate = 0.1
@@ -153,7 +199,7 @@ class DualGNN(UserGraphMixin, FusedEvalMixin, GeneralRecommender):
         self.MLP_t = nn.Linear(self.dim_latent, self.dim_latent, bias=False)
         self.load_user_graph(config, 40)
         inter = dataset.inter_matrix(form='coo').astype(np.float32)
-        self.graph = sym_norm_graph(inter, self.n_users, self.n_items, self.device)
+        self.graph = aggr_graph(self.aggr_mode, inter, self.n_users, self.n_items, self.device, "DualGNN")
         self.weight_u = nn.Parameter(np_xavier_normal(self.n_users, 2, 1))
         self.weight_u.data = F.softmax(self.weight_u.data, dim=1)
         self.weight_i = nn.Parameter(np_xavier_normal(self.n_items, 2, 1))
@@ -162,9 +208,9 @@ class DualGNN(UserGraphMixin, FusedEvalMixin, GeneralRecommender):
         self.MLP_user = nn.Linear(self.dim_latent * 3, self.dim_latent)
         self.v_preference = self.t_preference = None
         if self.v_feat is not None:
-            self.v_gcn = GCN(self.n_users, self.v_feat.size(1), self.dim_latent)
+            self.v_gcn = GCN(self.n_users, self.v_feat.size(1), self.dim_latent, self.aggr_mode)
         if self.t_feat is not None:
-            self.t_gcn = GCN(self.n_users, self.t_feat.size(1), self.dim_latent)
+            self.t_gcn = GCN(self.n_users, self.t_feat.size(1), self.dim_latent, self.aggr_mode)
         # float64 in the reference, and only ever read if evaluation precedes the first training step
         self.result_embed = nn.init.xavier_normal_(
             torch.tensor(np.random.randn(self.n_users + self.n_items, dim_x))).float().to(self.device)

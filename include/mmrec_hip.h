@@ -359,11 +359,16 @@ int mmrec_linear_fwd_split_f32(const float* X, const float* W, const float* b, f
  *       maximum's power of two (negligible against the sum unless the large entries' partners are exactly zero).  Stated, not
  *       guarded.
  * out == 64 and F % 128 == 0 run these kernels, every other shape is handed to mmrec_linear_bwd_w_f32 / mmrec_linear_bwd_x_f32.
+ * A db without a dW is MMREC_ERR_BAD_ARG for every shape, those handed to the fp32 entry points included, before any launch.
  * Deterministic (no float atomics).
  * workspace: mmrec_linear_bwd_split_workspace_bytes (>= mmrec_linear_workspace_bytes). */
 size_t mmrec_linear_bwd_split_workspace_bytes(int32_t n, int32_t F, int32_t out);
 int mmrec_linear_bwd_split_f32(const float* dY, const float* X, const float* W, float* dW, float* db, float* dX, int32_t n,
                                int32_t F, int32_t out, void* workspace, mmrec_stream_t stream);
+/* dW [out, F] = dY^T X, db [out] = column sums of dY (NULL: not wanted); out = 64 j, every 64-column group of dY in one launch.
+ * Returns, in this order and before any launch: out <= 0, out % 64 != 0, F <= 0 or F % 4 != 0: MMREC_ERR_UNSUPPORTED; n < 0:
+ * MMREC_ERR_BAD_ARG; NULL dW: MMREC_ERR_BAD_ARG; n == 0: dW = 0 (and db = 0 where given) are written, dY / X / workspace may be
+ * NULL; n > 0 with a NULL dY / X / workspace: MMREC_ERR_BAD_ARG. */
 int mmrec_linear_bwd_w_f32(const float* dY, const float* X, float* dW, float* db, int32_t n,
                            int32_t F, int32_t out, void* workspace, mmrec_stream_t stream);
 int mmrec_linear_bwd_x_f32(const float* dY, const float* W, float* dX, int32_t n, int32_t F,
@@ -387,7 +392,11 @@ int mmrec_linear_rows_fwd_f32(const float* T, int64_t n_table, const int64_t* id
 int mmrec_linear_rows_bwd_f32(const float* dY, const float* T, int64_t n_table, const int64_t* ids, const float* W, float* dW,
                               float* db, float* dX, int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream);
 /* C[M, :N] = A[M, K] B[N, K]^T (+ bias[N], may be NULL); K % 32 == 0, N <= ldc <= 2 Mi (32-bit byte offsets within a 128-row block).
- * F.linear(x, W, b) is (A, B) = (x, W); its dX is (A, B) = (dY, W^T). */
+ * F.linear(x, W, b) is (A, B) = (x, W); its dX is (A, B) = (dY, W^T).
+ * Only columns 0 .. N-1 of a row of C are written: columns N .. ldc-1 (ldc > N) are left untouched.
+ * Returns, in this order and before any launch: K <= 0, K % 32 != 0, N <= 0, ldc < N or ldc > 2^21: MMREC_ERR_UNSUPPORTED;
+ * M < 0: MMREC_ERR_BAD_ARG; M == 0: 0, no launch, nothing written (pointers may be NULL); NULL A / B / C: MMREC_ERR_BAD_ARG.
+ * Deterministic (no atomics). */
 int mmrec_gemm_nt_f32(const float* A, const float* B, const float* bias, float* C, int32_t M, int32_t N,
                       int32_t K, int32_t ldc, mmrec_stream_t stream);
 

@@ -1561,6 +1561,7 @@ namespace {
 int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const float* W, float* dW, float* db, float* dX,
                           int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream) {
     if (n < 0 || F <= 0 || out <= 0) return MMREC_ERR_BAD_ARG;
+    if (db && !dW) return MMREC_ERR_BAD_ARG;      // (before the hand-over: the fp32 entry points would leave db unwritten and return 0)
     if (!bwd_split_serves(n, F, out)) {
         if (dW) {
             const int rc = mmrec_linear_bwd_w_f32(dY, X, dW, db, n, F, out, workspace, stream);
@@ -1681,8 +1682,8 @@ extern "C" int mmrec_linear_rows_bwd_f32(const float* dY, const float* T, int64_
     return linear_bwd_split_impl(dY, T, g, W, dW, db, dX, n, F, out, workspace, stream);
 }
 
-// out = 64 j: the 64-column blocks of dY are handled one after the other (same workspace), each by
-// the out = 64 kernel with dY's row stride = out.
+// out = 64 j: every 64-column block of dY in ONE launch over grid.z, each by the out = 64 kernel with dY's
+// row stride = out and its own slab and db-partial region of the workspace.
 extern "C" int mmrec_linear_bwd_w_f32(const float* dY, const float* X, float* dW, float* db,
                                       int32_t n, int32_t F, int32_t out, void* workspace,
                                       mmrec_stream_t stream) {

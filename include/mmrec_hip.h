@@ -586,6 +586,53 @@ int mmrec_score_lse_f32(const float* Q, const float* K, int32_t B, int32_t N, in
 int mmrec_score_lse_bwd_f32(const float* Q, const float* K, int32_t B, int32_t N, int32_t d, float scale, const float* lse,
                             const float* g, float* dQ, float* dK, void* workspace, mmrec_stream_t stream);
 
+/* Hypergraph message passing of LGMRec: the Gumbel-softmax hyperedge assignment with its dropout, and the HGNN layer, each with
+ * its backward.  ADDITIVE to ABI 16: six new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: F.gumbel_softmax(x, tau, dim=1) and F.dropout of its result, and HGNNLayer's three torch.mm per layer --
+ *           lgmrec.py:23-36, 196-216 ([n, H] operands against a 64-wide table) -- and autograd's mirror of all of it.
+ * Served: 1 <= H <= 8, d == 64, fp32 row-major.  H outside that range or d != 64: MMREC_ERR_UNSUPPORTED, checked first.
+ *
+ * mmrec_hyper_assign_fwd_f32: logits, noise [n, H]; keep [n, H] of 0 / 1 floats or NULL; P [n, H]; p_soft [n, H] or NULL
+ *   p = softmax((logits + noise) / tau) over the H entries of a row, the row maximum subtracted (finite logits of any spread
+ *   give a finite p);  P = keep ? p * keep / keep_rate : p.  The kernel draws nothing: noise and keep are the caller's.
+ *   p_soft, where given, receives p: THE STATE THE BACKWARD NEEDS.  Without a mask P is p (pass P to the backward and NULL
+ *   here); with a mask P has lost p at the dropped entries, whose logits still get a gradient.  P must not be p_soft.
+ * mmrec_hyper_assign_bwd_f32: s = keep ? dP * keep / keep_rate : dP;  dlogits = p * (s - sum_h p_h s_h) / tau.
+ *   A row whose mask is all zero has P = 0 and dlogits = 0.  noise and keep get no gradient.
+ * Both: one launch, one thread per row.  n < 0: MMREC_ERR_BAD_ARG; n > 2^30: MMREC_ERR_UNSUPPORTED; n == 0: 0, no launch;
+ * a NULL logits / noise / P (p_soft / dP / dlogits): MMREC_ERR_BAD_ARG -- in this order, before any launch.
+ *
+ * mmrec_hyper_layer_fwd_f32: P_i [I, H], P_u [U, H], X_prev [I, 64] -> lat [H, 64], X_out [I, 64], U_out [U, 64]
+ *   lat = P_i^T X_prev;  X_out = P_i lat;  U_out = P_u lat.  U_out may be NULL (not wanted: every layer but the last); P_u is
+ *   then not read.  Three launches: reduce (one workgroup per mmrec_hyper_rows_per_block(I) consecutive rows: wave w of its
+ *   four walks the w-th quarter of the block in order, one column per lane and H fma accumulators; the four added in order),
+ *   finish (per hyperedge, wave k of sixteen adds the blocks k, k + 16, ... in order, the sixteen sums added in order) and
+ *   expand (out[r] = P[r][0] lat[0], then one fma per further hyperedge).  X_prev is read once, each output written once.
+ *   I == 0: lat = 0 and U_out = 0.  Outputs must not alias inputs.
+ * mmrec_hyper_layer_bwd_f32: given dU [U, 64] and dX [I, 64], either of which may be NULL (zeros):
+ *   dlat = P_i^T dX + P_u^T dU (the same reduce, item blocks then user blocks, and the same finish; kept in the workspace)
+ *   dP_i[r][h] = <dX[r], lat[h]> + <X_prev[r], dlat[h]>;   dP_u[r][h] = <dU[r], lat[h]>;   dX_prev = P_i dlat
+ *   Any of dP_i / dP_u / dX_prev may be NULL (not computed).  Three launches.
+ * Both: NO ATOMICS, every order fixed by the shape alone: two calls on the same inputs give the same bits.
+ * workspace: mmrec_hyper_workspace_bytes(I, U, H) bytes (16-byte aligned) serve either call: 512 floats and one H x 64 partial
+ * per block of either side; 0 for an unserved H or a negative size.  mmrec_hyper_rows_per_block(n): the rows one workgroup of
+ * the reduce walks for a side of n rows (a multiple of 64; 64 up to 131,072 rows; 0 for n < 0).
+ * I < 0 or U < 0: MMREC_ERR_BAD_ARG; I or U > 2^30: MMREC_ERR_UNSUPPORTED; a NULL lat / workspace, I > 0 with a NULL P_i /
+ * X_prev / X_out (backward: P_i, and X_prev where dP_i is wanted), U > 0 with a NULL P_u where U_out (dU) is given:
+ * MMREC_ERR_BAD_ARG -- in this order, before any launch.  No synchronisation, no allocation, no data-dependent launch shape,
+ * capture-safe, no global state. */
+int32_t mmrec_hyper_rows_per_block(int64_t n);
+size_t mmrec_hyper_workspace_bytes(int64_t I, int64_t U, int32_t H);
+int mmrec_hyper_assign_fwd_f32(const float* logits, const float* noise, const float* keep, int64_t n, int32_t H, float tau,
+                               float keep_rate, float* P, float* p_soft, mmrec_stream_t stream);
+int mmrec_hyper_assign_bwd_f32(const float* p_soft, const float* keep, const float* dP, int64_t n, int32_t H, float tau,
+                               float keep_rate, float* dlogits, mmrec_stream_t stream);
+int mmrec_hyper_layer_fwd_f32(const float* P_i, const float* P_u, const float* X_prev, int64_t I, int64_t U, int32_t H,
+                              int32_t d, float* U_out, float* X_out, float* lat, void* workspace, mmrec_stream_t stream);
+int mmrec_hyper_layer_bwd_f32(const float* P_i, const float* P_u, const float* X_prev, const float* lat, const float* dU,
+                              const float* dX, int64_t I, int64_t U, int32_t H, int32_t d, float* dP_i, float* dP_u,
+                              float* dX_prev, void* workspace, mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

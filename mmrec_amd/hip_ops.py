@@ -2626,6 +2626,157 @@ def score_lse(Q, K, scale=1.0):
 
 
 # ------------------------------------------------------------------------------------------------
+# Hypergraph message passing of LGMRec (csrc/hypergraph.hip): the Gumbel-softmax assignment with its dropout, the HGNN layer
+# ------------------------------------------------------------------------------------------------
+HYPER = True          # False: every hyper_* call is its `*_torch` composition (A/B runs)
+HYPER_H_MAX = 8       # hyperedges the kernels serve (Clothing's hyper_num = 64 takes the torch path)
+
+
+def hyper_rows_per_block(n):
+    """rows of a side of n rows that one workgroup of the layer's reduction walks (the library's plan)"""
+    return int(_lib.load().mmrec_hyper_rows_per_block(int(n)))
+
+
+def _hyper_table(t, width=None):
+    return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+                and t.shape[0] <= (1 << 30) and (t.shape[1] == width if width else 1 <= t.shape[1] <= HYPER_H_MAX))
+
+
+def hyper_assign_torch(logits, noise, keep_mask=None, tau=1.0, keep_rate=1.0):
+    """softmax((logits + noise) / tau) over dim 1, then `* keep_mask / keep_rate` where a mask is given: F.gumbel_softmax with
+    the noise supplied, F.dropout with the mask supplied.  The composition `hyper_assign` falls back to."""
+    p = ((logits + noise) / tau).softmax(1)
+    return p if keep_mask is None else p * keep_mask / keep_rate
+
+
+def hyper_assign_served(logits, noise, keep_mask=None):
+    """True where `hyper_assign` runs the kernels: device fp32 contiguous [n, H] operands of one shape, 1 <= H <= 8, the
+    `HYPER` switch on."""
+    return bool(HYPER and _hyper_table(logits) and _hyper_table(noise) and noise.shape == logits.shape and
+                (keep_mask is None or (_hyper_table(keep_mask) and keep_mask.shape == logits.shape)))
+
+
+class _HyperAssign(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, noise, keep, tau, keep_rate):
+        n, H = logits.shape
+        P = torch.empty_like(logits)
+        p = None if keep is None else torch.empty_like(logits)       # with a mask P has lost p at the dropped entries
+        _lib.check(_lib.load().mmrec_hyper_assign_fwd_f32(_p(logits), _p(noise), _p(keep), n, H, tau, keep_rate, _p(P), _p(p),
+                                                          _stream()), "hyper_assign_fwd")
+        ctx.tau, ctx.keep_rate, ctx.masked = tau, keep_rate, keep is not None
+        ctx.save_for_backward(*((p, keep) if ctx.masked else (P,)))
+        return P
+
+    @staticmethod
+    def backward(ctx, dP):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        p, keep = ctx.saved_tensors if ctx.masked else (ctx.saved_tensors[0], None)
+        n, H = p.shape
+        da = torch.empty_like(p)
+        _lib.check(_lib.load().mmrec_hyper_assign_bwd_f32(_p(p), _p(keep), _p(dP.contiguous()), n, H, ctx.tau, ctx.keep_rate,
+                                                          _p(da), _stream()), "hyper_assign_bwd")
+        return da, None, None, None, None
+
+
+def hyper_assign(logits, noise, keep_mask=None, tau=1.0, keep_rate=1.0):
+    """The hyperedge assignment of LGMRec (lgmrec.py:196-200 and the dropout of :208-209) -> P [n, H]:
+    p = softmax((logits + noise) / tau) over a row, P = p * keep_mask / keep_rate (no mask: P = p).  `noise` is the caller's
+    Gumbel draw and `keep_mask` its 0 / 1 dropout mask: nothing is drawn here.  Differentiable in `logits` only.
+    Served by the kernels (`hyper_assign_served`): one launch forward, one backward, the row maximum subtracted as torch does.
+    The state kept for the backward is p: without a mask that is the result itself; with a mask a second [n, H] tensor, because
+    the dropped entries of P are zero while their logits still get a gradient.
+    EVERY OTHER CASE (CPU tensors, H above 8 -- Clothing's 64 --, other dtypes, non-contiguous operands, the switch off) is
+    `hyper_assign_torch` with stock autograd."""
+    if hyper_assign_served(logits, noise, keep_mask):
+        return _HyperAssign.apply(logits, noise, keep_mask, float(tau), float(keep_rate))
+    return hyper_assign_torch(logits, noise, keep_mask, tau, keep_rate)
+
+
+def hyper_layer_torch(P_i, P_u, X):
+    """lat = P_i^T X;  X_out = P_i lat;  U_out = P_u lat -> (U_out, X_out): HGNNLayer's three torch.mm in its order"""
+    lat = torch.mm(P_i.T, X)
+    X_out = torch.mm(P_i, lat)
+    U_out = torch.mm(P_u, lat)
+    return U_out, X_out
+
+
+def hyper_layer_served(P_i, P_u, X):
+    """True where `hyper_layer` runs the kernels: device fp32 contiguous P_i [I, H], P_u [U, H], X [I, 64] with 1 <= H <= 8
+    and the `HYPER` switch on"""
+    return bool(HYPER and _hyper_table(P_i) and _hyper_table(P_u) and _hyper_table(X, EMB_DIM) and P_i.shape[1] == P_u.shape[1]
+                and P_i.shape[0] == X.shape[0])
+
+
+class _HyperLayer(torch.autograd.Function):
+    """forward(P_i, P_u or None where U_out is not wanted, X) -> (U_out or None, X_out)"""
+
+    @staticmethod
+    def forward(ctx, P_i, P_u, X):
+        lib = _lib.load()
+        (I, H), U = P_i.shape, 0 if P_u is None else P_u.shape[0]
+        lat = torch.empty(H, EMB_DIM, dtype=torch.float32, device=X.device)
+        X_out = torch.empty_like(X)
+        U_out = None if P_u is None else torch.empty(U, EMB_DIM, dtype=torch.float32, device=X.device)
+        ws = _ws(lib.mmrec_hyper_workspace_bytes(I, U, H), X.device)
+        _lib.check(lib.mmrec_hyper_layer_fwd_f32(_p(P_i), _p(P_u), _p(X), I, U, H, EMB_DIM, _p(U_out), _p(X_out), _p(lat), _p(ws),
+                                                 _stream()), "hyper_layer_fwd")
+        ctx.has_u = P_u is not None
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*((P_i, X, lat, P_u) if ctx.has_u else (P_i, X, lat)))
+        return U_out, X_out
+
+    @staticmethod
+    def backward(ctx, dU, dX):
+        P_i, X, lat = ctx.saved_tensors[:3]
+        P_u = ctx.saved_tensors[3] if ctx.has_u else None
+        want_pi, want_pu, want_x = ctx.needs_input_grad[0], ctx.has_u and ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want_pi or want_pu or want_x):
+            return None, None, None
+        lib = _lib.load()
+        (I, H), U = P_i.shape, 0 if P_u is None else P_u.shape[0]
+        dU = None if (dU is None or P_u is None) else dU.contiguous()
+        dX = None if dX is None else dX.contiguous()
+        dP_i = torch.empty_like(P_i) if want_pi else None
+        dP_u = torch.empty_like(P_u) if want_pu else None
+        dX_prev = torch.empty_like(X) if want_x else None
+        ws = _ws(lib.mmrec_hyper_workspace_bytes(I, U, H), X.device)
+        _lib.check(lib.mmrec_hyper_layer_bwd_f32(_p(P_i), _p(P_u), _p(X), _p(lat), _p(dU), _p(dX), I, U, H, EMB_DIM, _p(dP_i),
+                                                 _p(dP_u), _p(dX_prev), _p(ws), _stream()), "hyper_layer_bwd")
+        return dP_i, dP_u, dX_prev
+
+
+def hyper_layer(P_i, P_u, X):
+    """One HGNN layer of LGMRec (lgmrec.py:23-36) -> (U_out [U, 64], X_out [I, 64]):
+    lat = P_i^T X [H, 64];  X_out = P_i lat;  U_out = P_u lat, differentiable in all three operands.
+    Served by the kernels (`hyper_layer_served`): three launches each way (reduce over blocks of `hyper_rows_per_block` rows,
+    a finish that adds the blocks' partials in a fixed order, one row pass), X read once and each output written once, lat
+    [H, 64] the only state besides the operands.  No atomics: the same bits every call, so `DETERMINISTIC` changes nothing.
+    EVERY OTHER CASE (CPU tensors, H above 8, a width other than 64, other dtypes, non-contiguous operands, the switch off) is
+    `hyper_layer_torch` with stock autograd."""
+    if hyper_layer_served(P_i, P_u, X):
+        return _HyperLayer.apply(P_i, P_u, X)
+    return hyper_layer_torch(P_i, P_u, X)
+
+
+def hyper_propagate(P_i, P_u, E, n_layers):
+    """`n_layers` HGNN layers from X_0 = E -> (U_L, X_L): HGNNLayer.forward.  Only the last layer's U is a result, so the
+    served path asks the earlier layers for X alone (their user rows are neither computed nor written)."""
+    if n_layers < 1:
+        raise _lib.MMRecHipError("hyper_propagate: n_layers must be at least 1, got %r" % (n_layers,))
+    if not hyper_layer_served(P_i, P_u, E):
+        X = E
+        for _ in range(n_layers):
+            U_out, X = hyper_layer_torch(P_i, P_u, X)
+        return U_out, X
+    X = E
+    for _ in range(n_layers - 1):
+        _, X = _HyperLayer.apply(P_i, None, X)
+    return _HyperLayer.apply(P_i, P_u, X)
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

@@ -5,7 +5,13 @@ init   : binary user-item matrix R as a CSR (+ transpose for the backward), D^-1
 forward: CGE = fused LightGCN layer mean; MGE = modal projection X W on the fp32 MFMA GEMM (W is stored [F, 64] as in
          the reference: transposed view per step), R X on the CSR SpMM, n_mm propagation layers on the same kernel;
          hyperedge assignment X V (F x 4: a skinny library GEMM), R (X V) on the SpMM (4 columns padded to a 64-float
-         row), Gumbel-softmax and the 4-hyperedge HGNN products in torch (I x 4 and U x 4 operands)
+         row), Gumbel-softmax and the 4-hyperedge HGNN products in torch (I x 4 and U x 4 operands).  With the config key
+         `fused_hyper: True` (absent / False: that path, untouched) the assignment -- softmax of (logits + Gumbel noise) / tau
+         with the dropout mask and 1 / keep_rate -- is `hip_ops.hyper_assign` (one launch each way) and the HGNN layers are
+         `hip_ops.hyper_propagate` (csrc/hypergraph.hip: lat = P_i^T X reduced over row blocks in a fixed order, both outputs
+         expanded in one pass; no atomics).  The kernels draw nothing: `_hyper_noise` and `_hyper_keep` draw what
+         F.gumbel_softmax and F.dropout draw -- the same distributions, NOT the same generator stream, so a seeded run with
+         the key on is not step-identical to one with it off.  hyper_num above 8 (Clothing: 64) takes the torch composition
 loss   : fused BPR + EmbLoss on the batch rows; the hypergraph contrastive term scores the batch against EVERY
          user / item (B x N logits, lgmrec.py:157-164), not in-batch: torch matmul.  With the config key `fused_ssl: True`
          (absent / False: that path, untouched) the term is `hip_ops.score_lse` -- the row-wise log-sum-exp on the fp32 MFMA
@@ -56,6 +62,7 @@ class LGMRec(FusedEvalMixin, GeneralRecommender):
         self.reg_weight = config['reg_weight']
         self.tau = 0.2
         self.fused_ssl = bool(config['fused_ssl']) if 'fused_ssl' in config else False    # new key, default off
+        self.fused_hyper = bool(config['fused_hyper']) if 'fused_hyper' in config else False    # new key, default off
         self.n_nodes = self.n_users + self.n_items
         self.hgnnLayer = HGNNLayer(self.n_hyper_layer)
 
@@ -101,7 +108,39 @@ class LGMRec(FusedEvalMixin, GeneralRecommender):
         u_h = hip_ops.spmm(self.adj, i_h)
         return (F.gumbel_softmax(i_h, self.tau, dim=1, hard=False), F.gumbel_softmax(u_h, self.tau, dim=1, hard=False))
 
+    def _hyper_noise(self, logits):
+        """Gumbel(0, 1) noise of the logits' shape, drawn as F.gumbel_softmax draws it: -log(Exp(1))"""
+        return -torch.empty_like(logits, memory_format=torch.legacy_contiguous_format).exponential_().log()
+
+    def _hyper_keep(self, x):
+        """the 0 / 1 mask F.dropout(x, 1 - keep_rate) would draw: Bernoulli(keep_rate); None in eval mode (no dropout)"""
+        if not self.training:
+            return None
+        return torch.bernoulli(torch.full_like(x, self.keep_rate))
+
+    def _forward_fused_hyper(self):
+        """`forward` with `fused_hyper: True`: the same mathematics through hip_ops.hyper_assign / hyper_propagate.  The noise
+        is drawn in the reference's order (iv, uv, it, ut), then the masks in the same order; the draws follow F.gumbel_softmax's
+        and F.dropout's distributions but not their generator stream, so a seeded run is not step-identical to the key-off path."""
+        logits = []
+        for feat, w in ((self.image_embedding.weight, self.v_hyper), (self.text_embedding.weight, self.t_hyper)):
+            i_h = torch.mm(feat, w)
+            logits += [i_h, hip_ops.spmm(self.adj, i_h).contiguous()]    # (the SpMM's result is a view of its 64-float rows)
+        noise = [self._hyper_noise(a) for a in logits]
+        cge_embs = self.cge()
+        lge_embs = cge_embs + F.normalize(self.mge('v')) + F.normalize(self.mge('t'))
+        keep = [self._hyper_keep(a) for a in logits]
+        iv_p, uv_p, it_p, ut_p = (hip_ops.hyper_assign(a, g, m, self.tau, self.keep_rate) for a, g, m in zip(logits, noise, keep))
+        items = cge_embs[self.n_users:]
+        uv, iv = hip_ops.hyper_propagate(iv_p, uv_p, items, self.n_hyper_layer)
+        ut, it = hip_ops.hyper_propagate(it_p, ut_p, items, self.n_hyper_layer)
+        ghe_embs = torch.cat([uv, iv], dim=0) + torch.cat([ut, it], dim=0)
+        all_embs = lge_embs + self.alpha * F.normalize(ghe_embs)
+        return all_embs[:self.n_users], all_embs[self.n_users:], [uv, iv, ut, it]
+
     def forward(self):
+        if self.fused_hyper:
+            return self._forward_fused_hyper()
         iv_hyper, uv_hyper = self._hyper(self.image_embedding.weight, self.v_hyper)
         it_hyper, ut_hyper = self._hyper(self.text_embedding.weight, self.t_hyper)
         cge_embs = self.cge()

@@ -121,8 +121,12 @@ def main():
                                                              "hip_ops.score_lse instead of the B x N torch matrix)")
     ap.add_argument("--fused-ssl-ab", type=int, metavar="RUNS", help="lgmrec / pgl_cl: RUNS runs with fused_ssl on and RUNS with it off, "
                                                                      "alternated in this process; ms per batch of each and its spread")
+    ap.add_argument("--fused-hyper-ab", type=int, metavar="RUNS", help="lgmrec: RUNS runs with fused_hyper on (hip_ops.hyper_assign / "
+                                                                       "hyper_propagate) and RUNS with it off, alternated in this process")
     args = ap.parse_args()
     cd = dict(device_neg_sampling=args.device_neg_sampling)
+    if args.fused_hyper_ab and args.config != "lgmrec":
+        ap.error("fused_hyper is a key of LGMRec: use it with `lgmrec`")
     if args.fused_ssl or args.fused_ssl_ab:
         if args.config not in ("lgmrec", "pgl", "pgl_cl"):
             ap.error("fused_ssl is a key of LGMRec and PGL: use it with `lgmrec` or `pgl_cl` (`pgl` has the term's weight at 0)")
@@ -169,6 +173,17 @@ def main():
         for on in (True, False):
             v = sorted(ms[on])
             print("[%s] fused_ssl %-5s ms/batch median %.3f min %.3f max %.3f (spread %.3f) over %d runs" % (
+                args.config, on, v[len(v) // 2], v[0], v[-1], v[-1] - v[0], len(v)), flush=True)
+        return
+    if args.fused_hyper_ab:
+        ms = {True: [], False: []}
+        for i in range(2 * args.fused_hyper_ab):
+            on = i % 2 == 0
+            ms[on].append(run(args.config, dict(cd, fused_hyper=on), args.epochs, verbose=False)["ms_per_batch"])
+            print("[%s] run %d fused_hyper %s: %.3f ms/batch" % (args.config, i // 2, on, ms[on][-1]), flush=True)
+        for on in (True, False):
+            v = sorted(ms[on])
+            print("[%s] fused_hyper %-5s ms/batch median %.3f min %.3f max %.3f (spread %.3f) over %d runs" % (
                 args.config, on, v[len(v) // 2], v[0], v[-1], v[-1] - v[0], len(v)), flush=True)
         return
     if args.json:

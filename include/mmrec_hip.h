@@ -633,6 +633,55 @@ int mmrec_hyper_layer_bwd_f32(const float* P_i, const float* P_u, const float* X
                               const float* dX, int64_t I, int64_t U, int32_t H, int32_t d, float* dP_i, float* dP_u,
                               float* dX_prev, void* workspace, mmrec_stream_t stream);
 
+/* SMORE's spectrum step: rfft of two [n, 64] tables, three complex filters, three irfft, with its backward.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: torch.fft.rfft(dim=1, norm='ortho') of the image and text tables, the element-wise products with
+ *           view_as_complex of the three [1, 33, 2] weights (image, text, and text_fft * image_fft for the fusion filter) and the
+ *           three torch.fft.irfft(n=64) -- smore.py:188-206 -- and autograd's mirror of it.
+ * Served: d == 64, n <= 2^30, fp32 row-major; anything else: MMREC_ERR_UNSUPPORTED, checked first.
+ *
+ * Per row, with x the image and y the text row, (a, b) = rfft(x), (c, e) = rfft(y) as real / imaginary parts of the 33 bins:
+ *   p3 = c a - e b, q3 = c b + e a;   filter (p, q) with w = (wr, wi):  P = p wr - q wi, Q = p wi + q wr, out = irfft(P, Q)
+ *   out_img = filter((a, b), w_img), out_txt = filter((c, e), w_txt), out_fus = filter((p3, q3), w_fus).
+ * Weights are [33][2] interleaved (re, im): the memory of the model's [1, 33, 2] parameter.  The imaginary parts of bins 0 and
+ * 32 do not enter a real inverse: those two imaginary weights are NEVER READ (no output bit depends on them) and their
+ * gradients are written as exactly 0.0.
+ *
+ * THE PLAN.  A row's spectrum is packed into 64 floats (re_0 .. re_32, im_1 .. im_31), so every transform is a [rows, 64] x
+ * [64, 64] product with F[j][k] = cos(2 pi j k / 64) / 8, F[j][32 + k] = -sin(2 pi j k / 64) / 8 or its transpose; the factor 2
+ * of the inverse's bins 1 .. 31 is applied in the filter, exactly.  Twiddles: one table of cos(2 pi j / 64) rounded from
+ * float64 with exact 0 and +-1, indexed (j k) & 63, scaled by the power of two 1 / 8.  One workgroup per block of
+ * mmrec_spectrum_rows_per_block(n) consecutive rows (a multiple of 64; 64 up to 65,536 rows, at most 1,024 blocks), walked in
+ * tiles of 64 rows that stay in LDS.  A product ("stage") is one fma chain of 64 terms from 0 per output, the summed index
+ * ascending: 64 roundings, and the matrix entry's own counted as 2: S = 66.  Every filter expression is one multiply and one fma.
+ * mmrec_spectrum_fwd_f32: ONE launch; x and y read once, each output written once.  Roundings a term of an output meets:
+ *   out_img / out_txt: S + 2 + S = 134;   out_fus: (S + S) + 2 + 2 + S = 202.
+ * mmrec_spectrum_bwd_f32: given g_img, g_txt, g_fus [n, 64], each of which may be NULL (zeros; its transform is skipped):
+ *   (dP, dQ) = g F scaled as the inverse;  dwr = sum_rows (dP p + dQ q), dwi = sum_rows (-dP q + dQ p);
+ *   dp = dP wr + dQ wi, dq = -dP wi + dQ wr;  image: da += dp, db += dq;  text: dc += dp, de += dq;
+ *   fusion: da += dp c + dq e, db += -dp e + dq c, dc += dp a + dq b, de += -dp b + dq a;  dx = (da, db) F^T, dy = (dc, de) F^T.
+ *   The spectra are RECOMPUTED from x and y: the state between the two calls is x, y and the weights.  Two launches: the main
+ *   pass, which leaves one [3][33][2] partial per block in the workspace, and the finish (not launched where no weight gradient
+ *   is wanted), in which lane l of a wave adds the blocks l, l + 64, ... in order and a fixed butterfly adds the 64 lanes.
+ *   Roundings: dx / dy: 3 S + 4 = 202;  a weight gradient: 134 (image, text) or 202 (fusion) for the term, then
+ *   rows_per_block / 64 + 6 in the block and ceil(blocks / 64) + 6 in the finish.
+ *   Any of dx, dy, dw_img, dw_txt, dw_fus may be NULL (not computed).  A wanted gradient that no given g reaches is written as
+ *   zeros (dw_img with g_img NULL).
+ * NO ATOMICS, every order fixed by n alone: two calls on the same inputs give the same bits.
+ * workspace: mmrec_spectrum_workspace_bytes(n) bytes (16-byte aligned), 198 floats per block; 0 for n < 0 or n > 2^30; needed
+ * only where a weight gradient is wanted.  Outputs must not alias inputs.
+ * d != 64 or n > 2^30: MMREC_ERR_UNSUPPORTED; n < 0: MMREC_ERR_BAD_ARG; n == 0: 0, no launch; a NULL x / y / weight / forward
+ * output, or a NULL workspace where a weight gradient is wanted: MMREC_ERR_BAD_ARG -- in this order, before any pointer is
+ * followed.  No synchronisation, no allocation, no data-dependent launch shape, capture-safe (the first call on a device raises
+ * the kernels' LDS limit: make one call before capturing). */
+int32_t mmrec_spectrum_rows_per_block(int64_t n);
+size_t mmrec_spectrum_workspace_bytes(int64_t n);
+int mmrec_spectrum_fwd_f32(const float* x, const float* y, const float* w_img, const float* w_txt, const float* w_fus, int64_t n,
+                           int32_t d, float* out_img, float* out_txt, float* out_fus, mmrec_stream_t stream);
+int mmrec_spectrum_bwd_f32(const float* x, const float* y, const float* w_img, const float* w_txt, const float* w_fus,
+                           const float* g_img, const float* g_txt, const float* g_fus, int64_t n, int32_t d, float* dx, float* dy,
+                           float* dw_img, float* dw_txt, float* dw_fus, void* workspace, mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

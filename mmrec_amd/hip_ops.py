@@ -10,6 +10,7 @@ Reference call sites each op replaces are cited in include/mmrec_hip.h.
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -2774,6 +2775,112 @@ def hyper_propagate(P_i, P_u, E, n_layers):
     for _ in range(n_layers - 1):
         _, X = _HyperLayer.apply(P_i, None, X)
     return _HyperLayer.apply(P_i, P_u, X)
+
+
+# ------------------------------------------------------------------------------------------------
+# SMORE's spectrum step (csrc/spectrum.hip): rfft of two tables, three complex filters, three irfft
+# ------------------------------------------------------------------------------------------------
+SPECTRUM = True       # False: every spectrum_fusion call is `spectrum_fusion_torch` (A/B runs)
+SPECTRUM_BINS = EMB_DIM // 2 + 1
+_RDFT = {}            # (width, device) -> the four real DFT matrices of spectrum_fusion_torch
+
+
+def spectrum_rows_per_block(n):
+    """rows of a table of n rows that one workgroup of the spectrum kernels walks (the library's plan)"""
+    return int(_lib.load().mmrec_spectrum_rows_per_block(int(n)))
+
+
+def rdft_matrices(d, device):
+    """rfft(x) = x @ C + i x @ S, irfft(Re, Im) = Re @ Ci + Im @ Si for norm='ortho', n = d (even);
+    the DC / Nyquist imaginary parts do not contribute to the inverse, as in a C2R transform."""
+    n = torch.arange(d, dtype=torch.float64).unsqueeze(1)
+    k = torch.arange(d // 2 + 1, dtype=torch.float64).unsqueeze(0)
+    ang = 2.0 * math.pi * n * k / d
+    s = 1.0 / math.sqrt(d)
+    wk = torch.full((d // 2 + 1, 1), 2.0, dtype=torch.float64)
+    wk[0, 0] = wk[-1, 0] = 1.0
+    Si = -wk * torch.sin(ang).t() * s
+    Si[0, :] = 0.0
+    Si[-1, :] = 0.0
+    mats = (torch.cos(ang) * s, -torch.sin(ang) * s, wk * torch.cos(ang).t() * s, Si)
+    return tuple(m.to(torch.float32).to(device) for m in mats)
+
+
+def spectrum_fusion_torch(image, text, w_img, w_txt, w_fus):
+    """SMORE.spectrum_convolution as a function of its five operands: the same operations in the same order.  The
+    composition `spectrum_fusion` falls back to."""
+    key = (image.shape[1], image.device)
+    if key not in _RDFT:
+        _RDFT[key] = rdft_matrices(*key)
+    C, S, Ci, Si = _RDFT[key]
+    ir, ii = image @ C, image @ S
+    tr, ti = text @ C, text @ S
+
+    def filt(re, im, w):
+        wr, wi = w[0, :, 0], w[0, :, 1]
+        return (re * wr - im * wi) @ Ci + (re * wi + im * wr) @ Si
+    fr, fi = tr * ir - ti * ii, tr * ii + ti * ir
+    return filt(ir, ii, w_img), filt(tr, ti, w_txt), filt(fr, fi, w_fus)
+
+
+def spectrum_fusion_served(image, text, w_img, w_txt, w_fus):
+    """True where `spectrum_fusion` runs the kernels: device fp32 contiguous [I, 64] tables of one shape, 1 <= I <= 2^30,
+    device fp32 contiguous [1, 33, 2] weights, the `SPECTRUM` switch on."""
+    def table(t):
+        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
+                    t.is_contiguous() and t.shape[1] == EMB_DIM and 1 <= t.shape[0] <= (1 << 30))
+
+    def weight(t):
+        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                    tuple(t.shape) == (1, SPECTRUM_BINS, 2))
+    return bool(SPECTRUM and table(image) and table(text) and image.shape == text.shape and image.device == text.device
+                and all(weight(w) and w.device == image.device for w in (w_img, w_txt, w_fus)))
+
+
+class _SpectrumFusion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, text, w_img, w_txt, w_fus):
+        n = image.shape[0]
+        outs = tuple(torch.empty_like(image) for _ in range(3))
+        _lib.check(_lib.load().mmrec_spectrum_fwd_f32(_p(image), _p(text), _p(w_img), _p(w_txt), _p(w_fus), n, EMB_DIM,
+                                                      _p(outs[0]), _p(outs[1]), _p(outs[2]), _stream()), "spectrum_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(image, text, w_img, w_txt, w_fus)      # the spectra are recomputed: nothing else is kept
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_img, g_txt, g_fus):
+        image, text, w_img, w_txt, w_fus = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        if not any(want) or (g_img is None and g_txt is None and g_fus is None):
+            return None, None, None, None, None
+        lib = _lib.load()
+        n = image.shape[0]
+        gs = [None if g is None else g.contiguous() for g in (g_img, g_txt, g_fus)]
+        dx = torch.empty_like(image) if want[0] else None
+        dy = torch.empty_like(text) if want[1] else None
+        dws = [torch.empty_like(w) if want[2 + i] else None for i, w in enumerate((w_img, w_txt, w_fus))]
+        ws = _ws(lib.mmrec_spectrum_workspace_bytes(n), image.device) if any(want[2:]) else None
+        _lib.check(lib.mmrec_spectrum_bwd_f32(_p(image), _p(text), _p(w_img), _p(w_txt), _p(w_fus), _p(gs[0]), _p(gs[1]),
+                                              _p(gs[2]), n, EMB_DIM, _p(dx), _p(dy), _p(dws[0]), _p(dws[1]), _p(dws[2]), _p(ws),
+                                              _stream()), "spectrum_bwd")
+        return dx, dy, dws[0], dws[1], dws[2]
+
+
+def spectrum_fusion(image, text, w_img, w_txt, w_fus):
+    """SMORE's spectrum step (smore.py:188-206) -> (image_conv, text_conv, fusion_conv), each [I, 64]:
+    irfft(rfft(image) * w_img), irfft(rfft(text) * w_txt), irfft(rfft(text) * rfft(image) * w_fus) along dim 1 with
+    norm='ortho', the weights [1, 33, 2] as (re, im) pairs.  Differentiable in all five operands.
+    Served by the kernels (`spectrum_fusion_served`): one launch forward, two backward (the main pass and the finish that adds
+    the blocks' weight-gradient partials in a fixed order); both tables read once, each output written once, the spectra kept
+    in LDS and RECOMPUTED in the backward, so the state between the calls is the five operands.  An output that receives no
+    gradient costs no transform; an operand that needs none is not computed.  No atomics: the same bits every call, so
+    `DETERMINISTIC` changes nothing.  The imaginary weights of bins 0 and 32 are never read and get the gradient 0.0.
+    EVERY OTHER CASE (CPU tensors, a width other than 64, other dtypes, non-contiguous operands, an empty table, the switch
+    off) is `spectrum_fusion_torch` with stock autograd."""
+    if spectrum_fusion_served(image, text, w_img, w_txt, w_fus):
+        return _SpectrumFusion.apply(image, text, w_img, w_txt, w_fus)
+    return spectrum_fusion_torch(image, text, w_img, w_txt, w_fus)
 
 
 # ------------------------------------------------------------------------------------------------

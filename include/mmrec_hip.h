@@ -682,6 +682,34 @@ int mmrec_spectrum_bwd_f32(const float* x, const float* y, const float* w_img, c
                            const float* g_img, const float* g_txt, const float* g_fus, int64_t n, int32_t d, float* dx, float* dy,
                            float* dw_img, float* dw_txt, float* dw_fus, void* workspace, mmrec_stream_t stream);
 
+/* Top-k of a mix of three row softmaxes against three whole tables, never storing a [B, N] block: DAMRS's pseudo-labels.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: topk(p_a + p_b + 2 p_m, 10) with p = softmax(normalize(h[ids]) @ normalize(h).T, dim=1) for each of three
+ *           modalities -- damrs.py:141-180 -- and the nine [b, I] blocks behind it.
+ *   c_m[r, j] = <T_m[ids[r]], T_m[j]>                         T_0, T_1, T_2 [N, 64] fp32 row-major; ids [B] int64, or NULL:
+ *   S_t[r, j] = sum_m W[t][m] exp(c_m[r, j] - lse[m][r])      rows 0 .. B-1; lse [3][B] (the caller's: mmrec_score_lse_f32 of
+ *   list t of row r = the k columns j with the largest S_t    T_m[ids] against T_m at scale 1); W [3][3] on the device
+ * in score order, descending, ties by the lower column; out_idx [3][B][k] int32, out_val [3][B][k] (the scores; may be NULL).
+ * Scores are the fp32 fma chains of the fp32-input MFMA in natural k order, expf, and fma(W[t][2], p_2, fma(W[t][1], p_1,
+ * W[t][0] p_0)) -- the same roundings for every column, so bit-identical table rows score the same bits and tie by column.
+ * An id outside [0, N) is never used as an address: its three lists are -1 (values -inf).  A NaN score is never listed.
+ * Grid: 128-row tiles x column splits of mmrec_tri_topk_split_cols(B, N) columns (a function of B and N alone, at most 32
+ * splits; 0 for an empty table or a size above 2^30); every split keeps exact sorted lists and a finish kernel ranks their entries.  No atomics:
+ * two calls on the same inputs give the same bits.  workspace: mmrec_tri_topk_workspace_bytes(B, N, k) bytes, 16-byte aligned.
+ * k outside 1 .. 16, N < k, a negative size, a NULL table or lse: MMREC_ERR_BAD_ARG; B or N > 2^30: MMREC_ERR_UNSUPPORTED;
+ * B == 0: 0, no launch, nothing touched; a NULL W / out_idx / workspace: MMREC_ERR_BAD_ARG -- in this order, before any launch.
+ * mmrec_list_exclude_i32: out[r] [k] = the first k entries of cand[r] [kc] that do not occur in excl[r] [ke], in cand's order
+ * (R rows, one thread each).  kc - ke < k, k < 1 or a negative size: MMREC_ERR_BAD_ARG; R == 0: 0, no launch; a NULL cand / out
+ * / excl (with ke > 0): MMREC_ERR_BAD_ARG.
+ * All: no synchronisation, no allocation, no data-dependent launch shape, capture-safe, no global state. */
+int32_t mmrec_tri_topk_split_cols(int32_t B, int32_t N);
+size_t mmrec_tri_topk_workspace_bytes(int32_t B, int32_t N, int32_t k);
+int mmrec_tri_topk_f32(const float* T0, const float* T1, const float* T2, int32_t N, const int64_t* ids, int32_t B,
+                       const float* lse, const float* W, int32_t k, int32_t* out_idx, float* out_val, void* workspace,
+                       mmrec_stream_t stream);
+int mmrec_list_exclude_i32(const int32_t* cand, const int32_t* excl, int32_t R, int32_t kc, int32_t ke, int32_t k, int32_t* out,
+                           mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

@@ -2627,6 +2627,153 @@ def score_lse(Q, K, scale=1.0):
 
 
 # ------------------------------------------------------------------------------------------------
+# DAMRS's pseudo-labels (csrc/tri_topk.hip): top-k of a mix of three row softmaxes against three whole tables
+# ------------------------------------------------------------------------------------------------
+TRI_TOPK = True       # False: every tri_softmax_topk call is `tri_softmax_topk_torch`, pseudo_labels the dense composition (A/B runs)
+TRI_TOPK_KMAX = 16
+_DAMRS_W = {}         # device -> ones(3, 3) + eye(3)
+
+
+def tri_topk_split_cols(B, N):
+    """columns of the tables one workgroup of the sweep walks (the library's plan for the shape; 0 for empty tables)"""
+    return int(_lib.load().mmrec_tri_topk_split_cols(int(B), int(N)))
+
+
+def _tri_dev(t, dtype, shape):
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and
+            tuple(t.shape) == tuple(shape))
+
+
+def _tri_tables_served(tables, k):
+    if not (isinstance(tables, (tuple, list)) and len(tables) == 3 and isinstance(tables[0], torch.Tensor) and tables[0].dim() == 2):
+        return False
+    N = tables[0].shape[0]
+    return bool(all(_tri_dev(t, torch.float32, (N, EMB_DIM)) for t in tables) and 1 <= k <= TRI_TOPK_KMAX and k <= N <= (1 << 30))
+
+
+def tri_softmax_topk_served(tables, ids, lse, W, k):
+    """True where `tri_softmax_topk` runs the kernel: three device fp32 contiguous [N, 64] tables, N >= k, 1 <= k <= 16, ids None
+    or int64 [B] on the device, lse fp32 contiguous [3, B], W fp32 contiguous [3, 3], and the `TRI_TOPK` switch on."""
+    if not (TRI_TOPK and _tri_tables_served(tables, k) and isinstance(lse, torch.Tensor) and lse.dim() == 2):
+        return False
+    B = lse.shape[1]
+    return bool(B <= (1 << 30) and (ids is None or _tri_dev(ids, torch.int64, (B,))) and
+                _tri_dev(lse, torch.float32, (3, B)) and _tri_dev(W, torch.float32, (3, 3)))
+
+
+def tri_softmax_topk_torch(tables, ids, lse, W, k, return_values=False):
+    """the materialised composition of `tri_softmax_topk`: S_t = sum_m W[t][m] exp(T_m[ids] T_m^T - lse[m][:, None]) as [B, N]
+    blocks, sorted score descending with ties by the lower column; an id outside [0, N) gives -1 (values -inf)."""
+    N, B = tables[0].shape[0], lse.shape[1]
+    rows = torch.arange(B, device=lse.device) if ids is None else ids
+    ok = (rows >= 0) & (rows < N)
+    safe = torch.where(ok, rows, torch.zeros_like(rows))
+    p = [torch.exp(T[safe] @ T.t() - lse[m][:, None]) for m, T in enumerate(tables)]
+    idx, val = [], []
+    for t in range(3):
+        S = (W[t, 0] * p[0] + W[t, 1] * p[1]) + W[t, 2] * p[2]
+        v, i = torch.sort(S, dim=1, descending=True, stable=True)
+        idx.append(torch.where(ok[:, None], i[:, :k], torch.full_like(i[:, :k], -1)))
+        val.append(torch.where(ok[:, None], v[:, :k], torch.full_like(v[:, :k], float("-inf"))))
+    idx = torch.stack(idx)
+    return (idx, torch.stack(val)) if return_values else idx
+
+
+def _tri_topk_raw(tables, ids, lse, W, k, return_values):
+    lib = _lib.load()
+    N, B = tables[0].shape[0], lse.shape[1]
+    idx = torch.empty(3, B, k, dtype=torch.int32, device=lse.device)
+    val = torch.empty(3, B, k, dtype=torch.float32, device=lse.device) if return_values else None
+    ws = _ws(lib.mmrec_tri_topk_workspace_bytes(B, N, k), lse.device)
+    _lib.check(lib.mmrec_tri_topk_f32(_p(tables[0]), _p(tables[1]), _p(tables[2]), N, _p(ids), B, _p(lse), _p(W), k, _p(idx),
+                                      _p(val), _p(ws), _stream()), "tri_topk")
+    return idx, val
+
+
+def tri_softmax_topk(tables, ids, lse, W, k, return_values=False):
+    """For three tables T_m [N, 64] and query rows ids [B] (None: rows 0 .. B-1): list t of row r = the k columns j with the
+    largest S_t[r, j] = sum_m W[t][m] exp(<T_m[ids[r]], T_m[j]> - lse[m][r]) -> int64 [3, B, k] (and the scores), score
+    descending, ties by the lower column; lse [3, B] is the caller's log-sum-exp (`score_lse(T_m[ids], T_m, 1.0)`: S is then a
+    mix of the three row softmaxes).  DAMRS's mm_pos lists (damrs.py:141-150) with W = ones(3, 3) + eye(3), k = 10.
+    Served by the kernel (`tri_softmax_topk_served`): one sweep that never stores a [B, N] block, the same bits every call.
+    No autograd: the labels carry no gradient in the reference.
+    EVERY OTHER CASE (CPU tensors, other widths or dtypes, k > 16, the switch off) is `tri_softmax_topk_torch`, the materialised
+    composition with the same tie rule: a fallback, not a CPU path of the kernel."""
+    with torch.no_grad():
+        if tri_softmax_topk_served(tables, ids, lse, W, k):
+            idx, val = _tri_topk_raw(tables, ids, lse, W, k, return_values)
+            return (idx.long(), val) if return_values else idx.long()
+        return tri_softmax_topk_torch(tables, ids, lse, W, k, return_values)
+
+
+def list_exclude(cand, excl, k):
+    """row r of the result [R, k]: the first k entries of cand[r] that do not occur in excl[r], in cand's order (int32 device
+    lists, cand [R, kc], excl [R, ke], kc - ke >= k: mmrec_list_exclude_i32)"""
+    lib = _lib.load()
+    cand, excl = _chk(cand, torch.int32, "cand", 2), _chk(excl, torch.int32, "excl", 2)
+    if cand.shape[0] != excl.shape[0]:
+        raise _lib.MMRecHipError("list_exclude: one row of excl per row of cand")
+    out = torch.empty(cand.shape[0], k, dtype=torch.int32, device=cand.device)
+    _lib.check(lib.mmrec_list_exclude_i32(_p(cand), _p(excl), cand.shape[0], cand.shape[1], excl.shape[1], k, _p(out), _stream()),
+               "list_exclude")
+    return out
+
+
+def pseudo_labels_torch(tables, ids, k=10):
+    """DAMRS's labels as its dense path computes them (damrs.py:141-150 on [b, N] blocks): p_m = softmax(T_m[ids] T_m^T), for
+    target m with the others a, b: mm_pos = topk(p_a + p_b + p_m + p_m, k), single_pos = topk(p_m with mm_pos zeroed, k)."""
+    with torch.no_grad():
+        p = [torch.softmax(torch.mm(T[ids], T.t()), dim=1) for T in tables]
+        mm, single = [], []
+        for a, b, m in ((1, 2, 0), (0, 2, 1), (0, 1, 2)):      # the operand order of DAMRS.calculate_loss
+            mm_pos = torch.topk(p[a] + p[b] + p[m] + p[m], k, dim=-1).indices
+            mm.append(mm_pos)
+            single.append(torch.topk(p[m].scatter(1, mm_pos, 0.0), k, dim=-1).indices)
+        return torch.stack(mm), torch.stack(single)
+
+
+PSEUDO_TOPK_BLOCK_BYTES = 64 << 20    # score_topk sizes a [queries, N] fp32 score block inside its workspace
+
+
+def _top_cosines(Q, T, k2):
+    """score_topk(Q, T, k2) in blocks of query rows (a multiple of 128, at least 128) whose score block stays within
+    PSEUDO_TOPK_BLOCK_BYTES, the candidate side prepared once: the workspace never holds b x N scores"""
+    rows = max(128, PSEUDO_TOPK_BLOCK_BYTES // (4 * (-(-T.shape[0] // 256) * 256)) // 128 * 128)
+    if Q.shape[0] <= rows:
+        return score_topk(Q, T, k2)
+    cand = TopkCandidates(T)
+    return torch.cat([score_topk(Q[r0:r0 + rows], cand, k2) for r0 in range(0, Q.shape[0], rows)])
+
+
+def pseudo_labels(tables, ids, k=10):
+    """DAMRS's pseudo-labels for item rows ids [b] of three ROW-NORMALISED tables (text, image, session) [N, 64] ->
+    (mm_pos, single_pos), int64 [3, b, k] each, list t for target modality t -- without a [b, N] block.  Served (device fp32
+    contiguous tables of width 64, int64 device ids, N >= 2 k, k <= 16, `TRI_TOPK` on), under no_grad:
+      lse_m = score_lse(T_m[ids], T_m, 1.0)                       the three softmax denominators
+      mm_pos = tri_softmax_topk(tables, ids, lse, ones + eye, k)  top-k of p_a + p_b + 2 p_m
+      single_pos = the first k of score_topk(T_m[ids], T_m, 2 k) that are not in mm_pos[m]   (`_top_cosines`: in blocks of rows)
+    -- p_m is positive and monotone in the cosine within a row, so the top-k of p_m with k entries zeroed lies inside the
+    top-2k of the cosines.  Where N < 2 k or anything is unserved: `pseudo_labels_torch`, the dense composition."""
+    with torch.no_grad():
+        N = tables[0].shape[0] if isinstance(tables[0], torch.Tensor) and tables[0].dim() == 2 else 0
+        dev_ids = isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous()
+        if not (dev_ids and N >= 2 * k and ids.numel() > 0):
+            return pseudo_labels_torch(tables, ids, k)
+        if not (TRI_TOPK and _tri_tables_served(tables, k) and ids.numel() <= (1 << 30)):
+            return pseudo_labels_torch(tables, ids, k)
+        dev = ids.device
+        W = _DAMRS_W.get(dev)
+        if W is None:
+            W = _DAMRS_W[dev] = torch.ones(3, 3, device=dev) + torch.eye(3, device=dev)
+        Q = [T[ids] for T in tables]
+        lse = torch.stack([score_lse(q, T, 1.0) for q, T in zip(Q, tables)])
+        mm, _ = _tri_topk_raw(tables, ids, lse, W, k, False)
+        cand = torch.stack([_top_cosines(q, T, 2 * k) for q, T in zip(Q, tables)]).to(torch.int32)
+        single = list_exclude(cand.view(-1, 2 * k), mm.view(-1, k), k).view(3, -1, k)
+        return mm.long(), single.long()
+
+
+# ------------------------------------------------------------------------------------------------
 # Hypergraph message passing of LGMRec (csrc/hypergraph.hip): the Gumbel-softmax assignment with its dropout, the HGNN layer
 # ------------------------------------------------------------------------------------------------
 HYPER = True          # False: every hyper_* call is its `*_torch` composition (A/B runs)

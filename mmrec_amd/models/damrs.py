@@ -7,7 +7,10 @@ layer mean for LightGCN); evaluation is the fused score + mask + top-K.  The pse
 (row softmaxes / top-10 over [batch items, all items] similarity blocks, the neighbour-discrimination and KL terms,
 the confidence-weighted BPR) is dense row-wise work on those blocks and stays in torch; the positive scores of the
 discrimination term are read out of the similarity block instead of being re-computed from a gathered [b, 10, 64]
-tensor.
+tensor.  With the config key `fused_labels: True` (absent / False: that path, untouched) the neighbour term holds no
+[b, I] block: the labels come from `hip_ops.pseudo_labels` (csrc/tri_topk.hip: one sweep over the three tables for the
+three mixed top-10 lists, the second lists out of the top-20 cosines), the row totals from `hip_ops.score_lse` and the
+twenty positive cosines per row from `hip_ops.edge_dot`; the KL term's [users, items] blocks stay.
 
 Reference behaviour kept: image_trs / text_trs exist (and are saved) but take no part in anything; the weights stored
 in the item-graph file are ignored (a 0/1 adjacency is normalised); items missing from the file keep only their self
@@ -97,6 +100,7 @@ class DAMRS(FusedEvalMixin, GeneralRecommender):
                 s_rows.append(np.full(nb.shape[0], i, dtype=np.int64))
                 s_cols.append(nb)
         self.session_adj = sym_normalised_graph(np.concatenate(s_rows), np.concatenate(s_cols), self.n_items, self.device)
+        self.fused_labels = bool(config['fused_labels']) if 'fused_labels' in config else False    # new key, default off
 
     # ---- propagation
     def _item_graph(self, graph):
@@ -147,7 +151,43 @@ class DAMRS(FusedEvalMixin, GeneralRecommender):
             neg_w = torch.clamp((p.max(0).values - n_mean) * (p_mean < n_mean).to(p.dtype), 0, 1)
         return pos_w, neg_w
 
+    def _neighbour_fused(self, i_id, tables, k=10, temperature=0.2):
+        """the neighbour-discrimination term of the three modalities without a [b, I] block: labels from
+        hip_ops.pseudo_labels, log of the row total by score_lse, the 2 k positive cosines per row by edge_dot"""
+        hn = [hip_ops.row_normalize(h) for h in tables]
+        mm_pos, s_pos = hip_ops.pseudo_labels([x.detach() for x in hn], i_id, k)
+        rows = i_id.repeat_interleave(2 * k)
+        total = 0.0
+        for m, x in enumerate(hn):
+            log_ttl = hip_ops.score_lse(x[i_id], x, 1.0 / temperature)
+            cols = torch.cat((mm_pos[m], s_pos[m]), dim=1).reshape(-1)
+            e = torch.exp(hip_ops.edge_dot(x, x, rows, cols).view(-1, 2 * k) / temperature)
+            mm, s, ttl = e[:, :k].sum(1), e[:, k:].sum(1), torch.exp(log_ttl)
+            total = total + torch.mean(-torch.log(mm / ttl + 10e-10) - torch.log(s / (ttl - mm) + 10e-10))
+        return total / 3.0
+
+    def _calculate_loss_fused(self, interaction):
+        """calculate_loss with `fused_labels`: only the neighbour term differs, the KL and BPR terms are those below"""
+        users, pos_items, neg_items = interaction[0], interaction[1], interaction[2]
+        user_emb, item_emb, h_t, h_v, h_s = self.forward()
+        u_id = torch.unique(users)
+        i_id = torch.unique(torch.cat((pos_items, neg_items)))
+        neighbour = self._neighbour_fused(i_id, (h_t, h_v, h_s))
+        n_u = user_emb[u_id]
+        it_emb = (h_t + h_s + h_v) / 3.0
+        p_g = torch.sigmoid(torch.mm(n_u, F.normalize(item_emb[i_id], dim=-1).t()))
+        p_m = torch.sigmoid(torch.mm(n_u, F.normalize(it_emb[i_id], dim=-1).t()))
+        kl = torch.mean(self._kl(p_g, p_m) + self._kl(p_m, p_g))
+        u = user_emb[users]
+        pos_w, neg_w = self._modal_weights(u, h_t, h_v, h_s, pos_items, neg_items)
+        ia = item_emb + (h_t + h_v + h_s) / 3.0
+        diff = (u * ia[pos_items]).sum(1) - (u * ia[neg_items]).sum(1)
+        mf = -torch.mean(torch.log(torch.sigmoid(diff)) * pos_w + torch.log(torch.sigmoid(-diff)) * neg_w)
+        return mf + self.neighbor_weight * neighbour + kl * self.kl_weight
+
     def calculate_loss(self, interaction):
+        if self.fused_labels:
+            return self._calculate_loss_fused(interaction)
         users, pos_items, neg_items = interaction[0], interaction[1], interaction[2]
         user_emb, item_emb, h_t, h_v, h_s = self.forward()
         u_id = torch.unique(users)

@@ -436,7 +436,9 @@ int mmrec_edge_dot_bwd_f32(const float* g, const float* A, int64_t n_a, const fl
  *             derivative of the forward with the maximum detached; WRITES ds, does not add into it.
  * Rows of at most mmrec_segment_softmax_group_max() entries: one 16-lane group per row; longer rows: one workgroup per row,
  * taken from long_rows [n_long] (device, int32, ascending) -- exactly the rows longer than that constant, which is what
- * mmrec_spmm_plan_fill writes when called with the constant as its threshold.  A list that names other rows than those leaves
+ * mmrec_spmm_plan_fill writes when called with the constant as its threshold.  The constant is ONE value for the three per-row
+ * edge ops: mmrec_edge_attention_group_max() and mmrec_neighbor_max_group_max() return the same number, so one list per CSR
+ * serves all of them.  A list that names other rows than those leaves
  * entries of out unwritten (a device list cannot be checked here; hip_ops checks it on the host when it builds it).
  * n_long == 0 (long_rows may be NULL): the 16-lane groups serve every row, whatever its length.
  * No atomics, every sum in an order fixed by the row's length: both directions repeat bit for bit.  Empty rows write nothing.
@@ -465,9 +467,9 @@ int mmrec_segment_softmax_bwd_f32(const int32_t* rowptr, int32_t n_rows, const i
  *   Y[r]    = sum_p alpha_p * KV[colidx[j]]                             Y [n_rows, 64]
  * Q == KV is allowed; Y and alpha must not alias an input.  d == 64 only.  Rows of at most mmrec_edge_attention_group_max()
  * entries: one 16-lane group per row with an online (running-maximum) softmax; longer rows: one workgroup per row of long_rows
- * [n_long] (device, int32) -- the rows longer than that constant as mmrec_spmm_plan_fill lists them at that threshold; the
- * constant equals mmrec_segment_softmax_group_max(), so one list serves both.  n_long == 0: the groups serve every row.  A list
- * that names other rows leaves rows of Y unwritten (hip_ops checks it on the host).
+ * [n_long] (device, int32) -- the rows longer than that constant as mmrec_spmm_plan_fill lists them at that threshold
+ * (mmrec_segment_softmax_f32's list).  n_long == 0: the groups serve every row.  A list that names other rows leaves rows of Y
+ * unwritten (hip_ops checks it on the host).
  * EVERY row of Y is written (zeros for a row without edges).  A colidx outside [0, n_kv) or a position outside [0, n_edges) is
  * an absent edge: never an address, adds nothing, its alpha is not written.  No atomics: the bits of Y and alpha are a
  * function of the inputs and the row lengths.  A row whose scores hold a NaN, a +inf or nothing but -inf is NaN in every
@@ -531,9 +533,8 @@ int mmrec_edge_attention_bwd_f32(const int32_t* rowptr, int32_t n_rows, const in
  * chosen value's bits (the forward is exact).  A row without (present) entries: Y = 0 and arg = -1.  EVERY row of Y and of arg
  * is written.  A colidx outside [0, n_x) or a position outside [0, n_edges) is an absent edge: never an address, never chosen.
  * Rows of at most mmrec_neighbor_max_group_max() entries: one 16-lane group per row; longer rows: one workgroup per row of
- * long_rows [n_long] (device, int32; listed as for mmrec_edge_attention_f32 -- the constant equals
- * mmrec_segment_softmax_group_max(), so one list serves all three); n_long == 0: the groups serve every row.  A list that names
- * other rows leaves rows unwritten (hip_ops checks it on the host).  The result does not depend on the launch shape: partial
+ * long_rows [n_long] (device, int32; mmrec_segment_softmax_f32's list); n_long == 0: the groups serve every row.  A list that
+ * names other rows leaves rows unwritten (hip_ops checks it on the host).  The result does not depend on the launch shape: partial
  * states are combined by (is NaN, value, CSR slot).  No atomics.  Y and arg must not alias an input.
  * d != 64: MMREC_ERR_UNSUPPORTED; negative sizes: MMREC_ERR_BAD_ARG; n_rows == 0: 0 and no launch; n_edges or n_x > 2^31 - 1:
  * MMREC_ERR_UNSUPPORTED; a NULL rowptr / Y / arg, n_edges > 0 with a NULL colidx / X, n_long > 0 with NULL long_rows:

@@ -6,6 +6,7 @@ hipcc cross-compiles without a GPU.  No torch headers are involved: the library 
 (include/mmrec_hip.h)."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -37,12 +38,16 @@ def _newer(src_list, target):
     return any(os.path.getmtime(s) > t for s in src_list)
 
 
+def header_deps():
+    """the headers an edit of which recompiles every source: each *.h of csrc/ and the public header"""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.normpath(os.path.join(PKG, "..", "include", "mmrec_hip.h"))]
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
-    deps = [os.path.join(CSRC, h) for h in ("common.h", "mfma_stream.h", "topk_sort.h", "topk_filter.h", "spmm_narrow.h")] + [
-        os.path.join(PKG, "..", "include", "mmrec_hip.h")]
+    deps = header_deps()
     jobs = []
     for s in SOURCES:
         src, obj = os.path.join(CSRC, s), os.path.join(OBJ, s.replace(".hip", ".o"))

@@ -9,7 +9,7 @@
 //   group  16 lanes per row (four rows per wave, 16 per workgroup), lanes stride over the row's entries, maximum and sum by the
 //          DPP / ds_swizzle butterfly of common.h (xor 8, 4, 2, 1).  A term of the sum meets ceil(len / 16) roundings in its
 //          lane's chain and 4 in the butterfly.
-//   block  one 256-thread workgroup per LISTED row (rows longer than SEG_GROUP_MAX: the list of mmrec_spmm_plan_fill at that
+//   block  one 256-thread workgroup per LISTED row (rows longer than rg::GROUP_MAX: the list of mmrec_spmm_plan_fill at that
 //          threshold): the wave butterfly (xor 32 ... 1), then the four wave partials through LDS, added as (w0 + w1) + (w2 +
 //          w3).  ceil(len / 256) + 8 roundings.
 // The first KEEP entries of a lane stay in registers between the passes (rows of <= 64 entries at 16 lanes, <= 1024 at 256
@@ -18,17 +18,15 @@
 // of both directions repeat run after run.  Empty rows write nothing.  Non-finite scores follow the arithmetic: the maximum
 // skips NaN (v_max_f32), the NaN then enters the sum through exp; +inf or an all -inf row give inf - inf = NaN; so such a
 // row is NaN in every entry and no other row is touched, and a -inf next to a finite maximum is exp(-inf) = 0 exactly.
-#include "common.h"
+#include "row_groups.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int SEG_BLOCK = 256;
-constexpr int SEG_GROUP = 16;                   // lanes per short row
-constexpr int SEG_GROUP_MAX = 256;              // longer rows go to the block kernel (when the caller lists them)
+using rg::slot_pos;
+
 constexpr int SEG_KEEP = 4;                     // entries per lane kept in registers between the passes
-constexpr int SEG_MAX_BLOCKS = 2048;            // 8 resident 256-thread workgroups on each of 256 CUs; the loop strides the rest
 
 struct GroupReduce {
     __device__ __forceinline__ float max(float v) const {
@@ -42,7 +40,7 @@ struct GroupReduce {
 
 // every thread of the workgroup calls these (the row is the workgroup's)
 struct BlockReduce {
-    float* lds;                                  // SEG_BLOCK / 64 floats
+    float* lds;                                  // rg::BLOCK / 64 floats
     __device__ __forceinline__ float max(float v) const {
         v = fmaxf(v, lane_xor_f<32>(v));
         v = fmaxf(v, lane_xor_f<16>(v));
@@ -60,13 +58,6 @@ struct BlockReduce {
         return (lds[0] + lds[1]) + (lds[2] + lds[3]);
     }
 };
-
-// position of CSR slot j in the caller's arrays; a slot whose position is outside them is skipped, never used as an address
-__device__ __forceinline__ int slot_pos(const int64_t* __restrict__ perm, int j, int n_edges) {
-    if (!perm) return j;
-    const int64_t p = perm[j];
-    return (p >= 0 && p < n_edges) ? (int)p : -1;
-}
 
 // the row's slots are [start, end); lane t of LANES owns the slots start + t, start + t + LANES, ...
 template <int LANES, class Reduce>
@@ -141,54 +132,40 @@ __device__ __forceinline__ void row_softmax_bwd(int start, int end, int t, const
     }
 }
 
-// [start, end) of row r, clamped to the arrays
-__device__ __forceinline__ void row_span(const int32_t* __restrict__ rowptr, int r, int n_edges, int& start, int& end) {
-    start = rowptr[r];
-    end = rowptr[r + 1];
-    if (start < 0) start = 0;
-    if (end > n_edges) end = n_edges;
-}
-
 // BWD = false: a = score, b unused, c = eps; BWD = true: a = alpha, b = g
 template <bool BWD>
-__global__ __launch_bounds__(SEG_BLOCK) void segment_softmax_group_kernel(const int32_t* __restrict__ rowptr, int n_rows,
+__global__ __launch_bounds__(rg::BLOCK) void segment_softmax_group_kernel(const int32_t* __restrict__ rowptr, int n_rows,
                                                                           const int64_t* __restrict__ perm, bool skip_long,
                                                                           const float* __restrict__ a,
                                                                           const float* __restrict__ b, int n_edges, float eps,
                                                                           float* __restrict__ out) {
-    constexpr int GROUPS = SEG_BLOCK / SEG_GROUP;
-    const int t = threadIdx.x % SEG_GROUP;
-    const int stride = gridDim.x * GROUPS;
-    // the row -- and with it every branch around the butterflies -- is the same for the 16 lanes of a group
-    for (long r = (long)blockIdx.x * GROUPS + threadIdx.x / SEG_GROUP; r < n_rows; r += stride) {
-        int start, end;
-        row_span(rowptr, (int)r, n_edges, start, end);
-        if (end <= start || (skip_long && end - start > SEG_GROUP_MAX)) continue;
+    rg::for_short_rows(rowptr, n_rows, n_edges, skip_long, [&](long, int start, int end, int t) {
+        if (end <= start) return;
         if (BWD)
-            row_softmax_bwd<SEG_GROUP>(start, end, t, perm, a, b, n_edges, out, GroupReduce());
+            row_softmax_bwd<rg::LANES>(start, end, t, perm, a, b, n_edges, out, GroupReduce());
         else
-            row_softmax<SEG_GROUP>(start, end, t, perm, a, n_edges, eps, out, GroupReduce());
-    }
+            row_softmax<rg::LANES>(start, end, t, perm, a, n_edges, eps, out, GroupReduce());
+    });
 }
 
 template <bool BWD>
-__global__ __launch_bounds__(SEG_BLOCK) void segment_softmax_block_kernel(const int32_t* __restrict__ rowptr, int n_rows,
+__global__ __launch_bounds__(rg::BLOCK) void segment_softmax_block_kernel(const int32_t* __restrict__ rowptr, int n_rows,
                                                                           const int64_t* __restrict__ perm,
                                                                           const int32_t* __restrict__ long_rows,
                                                                           const float* __restrict__ a,
                                                                           const float* __restrict__ b, int n_edges, float eps,
                                                                           float* __restrict__ out) {
-    __shared__ float lds[SEG_BLOCK / MMREC_WAVE];
+    __shared__ float lds[rg::BLOCK / MMREC_WAVE];
     const int r = long_rows[blockIdx.x];
     if (r < 0 || r >= n_rows) return;                        // (the whole workgroup)
     int start, end;
-    row_span(rowptr, r, n_edges, start, end);
+    rg::row_span(rowptr, r, n_edges, start, end);
     if (end <= start) return;
     const BlockReduce red{lds};
     if (BWD)
-        row_softmax_bwd<SEG_BLOCK>(start, end, threadIdx.x, perm, a, b, n_edges, out, red);
+        row_softmax_bwd<rg::BLOCK>(start, end, threadIdx.x, perm, a, b, n_edges, out, red);
     else
-        row_softmax<SEG_BLOCK>(start, end, threadIdx.x, perm, a, n_edges, eps, out, red);
+        row_softmax<rg::BLOCK>(start, end, threadIdx.x, perm, a, n_edges, eps, out, red);
 }
 
 inline int seg_check(const int32_t* rowptr, int32_t n_rows, const int32_t* long_rows, int32_t n_long, const float* a,
@@ -204,20 +181,23 @@ inline int seg_check(const int32_t* rowptr, int32_t n_rows, const int32_t* long_
 template <bool BWD>
 int seg_launch(const int32_t* rowptr, int32_t n_rows, const int64_t* perm, const int32_t* long_rows, int32_t n_long,
                const float* a, const float* b, int64_t n_edges, float eps, float* out, mmrec_stream_t stream) {
-    constexpr int GROUPS = SEG_BLOCK / SEG_GROUP;
-    const int blocks = (n_rows + GROUPS - 1) / GROUPS;
     hipStream_t s = mmrec_stream(stream);
-    hipLaunchKernelGGL(segment_softmax_group_kernel<BWD>, dim3(blocks < SEG_MAX_BLOCKS ? blocks : SEG_MAX_BLOCKS),
-                       dim3(SEG_BLOCK), 0, s, rowptr, (int)n_rows, perm, n_long > 0, a, b, (int)n_edges, eps, out);
-    if (n_long > 0)
-        hipLaunchKernelGGL(segment_softmax_block_kernel<BWD>, dim3(n_long), dim3(SEG_BLOCK), 0, s, rowptr, (int)n_rows, perm,
-                           long_rows, a, b, (int)n_edges, eps, out);
+    rg::launch_pair(
+        n_rows, n_long,
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(segment_softmax_group_kernel<BWD>, grid, dim3(rg::BLOCK), 0, s, rowptr, (int)n_rows, perm,
+                               n_long > 0, a, b, (int)n_edges, eps, out);
+        },
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(segment_softmax_block_kernel<BWD>, grid, dim3(rg::BLOCK), 0, s, rowptr, (int)n_rows, perm,
+                               long_rows, a, b, (int)n_edges, eps, out);
+        });
     MMREC_RETURN_LAUNCH_STATUS();
 }
 
 }  // namespace
 
-extern "C" int32_t mmrec_segment_softmax_group_max(void) { return SEG_GROUP_MAX; }
+extern "C" int32_t mmrec_segment_softmax_group_max(void) { return rg::GROUP_MAX; }
 
 extern "C" int mmrec_segment_softmax_f32(const int32_t* rowptr, int32_t n_rows, const int64_t* perm, const int32_t* long_rows,
                                          int32_t n_long, const float* score, int64_t n_edges, float eps, float* out,

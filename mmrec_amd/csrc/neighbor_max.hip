@@ -12,12 +12,11 @@
 // ahead of its use), the ids go round the group by shuffle and NMAX_NB gathers are in flight per step (NMAX_NB_BLOCK in the
 // workgroup of a listed row).  Every lane sees every entry of its span in CSR order, so inside a group "first" needs no
 // exchange: an entry replaces the state only if it is NaN where the state is not, or strictly greater (nmax_take).
-//   group  four rows per wave, 16 per workgroup; rows of at most NMAX_GROUP_MAX entries, or every row when no list is given.
-//   block  one 256-thread workgroup per LISTED row (the list of mmrec_spmm_plan_fill at NMAX_GROUP_MAX, which equals the
-//          segment softmax's and the attention's constant: the list a DynGraph caches serves this op too): group g takes
-//          the slots 16 g ... 16 g + 15 of every 256; the 16 (value, slot) states go through LDS and the first wave, one
-//          column per lane, combines them by (is NaN, value, CSR slot) -- nmax_better -- so the result is the rule above and
-//          not "whichever group held it".
+//   group  four rows per wave, 16 per workgroup; rows of at most rg::GROUP_MAX entries, or every row when no list is given.
+//   block  one 256-thread workgroup per LISTED row (the list of mmrec_spmm_plan_fill at rg::GROUP_MAX, row_groups.h's one
+//          threshold: the list a DynGraph caches serves every op): group g takes the slots 16 g ... 16 g + 15 of every 256;
+//          the 16 (value, slot) states go through LDS and the first wave, one column per lane, combines them by (is NaN,
+//          value, CSR slot) -- nmax_better -- so the result is the rule above and not "whichever group held it".
 // A colidx outside [0, n_x) or a position outside [0, n_edges) is an absent edge: never an address, never chosen.  EVERY
 // row of Y and of arg is written.  No atomics: the bits are a function of the inputs alone (not even of the launch shape).
 //
@@ -29,30 +28,20 @@
 // the chosen copy contributes.  A row id outside [0, n_rows) or a position outside [0, n_edges) is an absent edge.  A term
 // that does not match is not added (not "added as 0"): a NaN in dY[r][c] reaches the one dX element its arg names.
 // Known and accepted, as in edge_attention.hip: a hub of tens of thousands of edges is ONE workgroup in each direction.
-#include "common.h"
+#include "row_groups.h"
 
 namespace {
 
-constexpr int NMAX_BLOCK = 256;
-constexpr int NMAX_GROUP = 16;                   // lanes per row: 64 columns as float4
-constexpr int NMAX_GROUPS = NMAX_BLOCK / NMAX_GROUP;
-constexpr int NMAX_GROUP_MAX = 256;              // = edge_softmax.hip's SEG_GROUP_MAX: a DynGraph's long-row list serves this op too
+using rg::slot_pos;
+
 constexpr int NMAX_NB = 4;                       // gathers in flight per group and step
 constexpr int NMAX_NB_BLOCK = 16;                // ... in the workgroup that owns a listed row: its latency is the call's tail
 constexpr int NMAX_NB_BLOCK_BWD = 8;             // ... of (arg, dY) row pairs in the backward's
-constexpr int NMAX_MAX_BLOCKS = 2048;            // 8 resident 256-thread workgroups on each of 256 CUs; the loop strides the rest
 
 struct MaxState {
     float4 v;                                    // the chosen values
     int4 s;                                      // their CSR slots, -1: nothing yet
 };
-
-// position of CSR slot j in the caller's arrays, -1 where it lies outside them
-__device__ __forceinline__ int nmax_pos(const int64_t* __restrict__ perm, int j, int n_edges) {
-    if (!perm) return j;
-    const int64_t p = perm[j];
-    return (p >= 0 && p < n_edges) ? (int)p : -1;
-}
 
 // An entry x of slot j that comes AFTER everything in (b, bs) in CSR order: it wins only if nothing was there, or if the
 // state is not NaN and x is NaN or strictly greater (!(x <= b) is both; -0 <= +0 and +0 <= -0: a tie keeps the first).
@@ -73,19 +62,12 @@ __device__ __forceinline__ bool nmax_better(float x, int xs, float b, int bs) {
     return x > b || (x == b && xs < bs);
 }
 
-__device__ __forceinline__ void nmax_span_of(const int32_t* __restrict__ rowptr, int r, int n_edges, int& start, int& end) {
-    start = rowptr[r];
-    end = rowptr[r + 1];
-    if (start < 0) start = 0;
-    if (end > n_edges) end = n_edges;
-}
-
 // the column id of slot j, -1 for a slot beyond the row or an absent edge
 __device__ __forceinline__ int nmax_col(int j, int end, const int32_t* __restrict__ colidx, const int64_t* __restrict__ perm,
                                         int n_edges, int n_x) {
     if (j < 0 || j >= end) return -1;                           // (j < 0: base + stride + t beyond int)
     const int c = colidx[j];
-    return (c < 0 || c >= n_x || nmax_pos(perm, j, n_edges) < 0) ? -1 : c;
+    return (c < 0 || c >= n_x || slot_pos(perm, j, n_edges) < 0) ? -1 : c;
 }
 
 // The slots first ... first + 15, first + stride ..., below end, of one row for one 16-lane group, in CSR order, NB gathers in
@@ -97,14 +79,14 @@ __device__ __forceinline__ void max_span(int first, int end, int stride, int t, 
     int c = first < end ? nmax_col(first + t, end, colidx, perm, n_edges, n_x) : -1;
     for (int base = first; base < end; base += stride) {
         const int c_next = end - base > stride ? nmax_col(base + stride + t, end, colidx, perm, n_edges, n_x) : -1;
-        const int cnt = min(NMAX_GROUP, end - base);
+        const int cnt = min(rg::LANES, end - base);
         for (int k0 = 0; k0 < cnt; k0 += NB) {
             float4 x[NB];
             int cs[NB];
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
-                cs[u] = __shfl(c, k0 + u, NMAX_GROUP);          // (-1 beyond cnt: those lanes hold -1)
-                x[u] = cs[u] >= 0 ? X4[(size_t)cs[u] * NMAX_GROUP + t] : f4_zero();
+                cs[u] = __shfl(c, k0 + u, rg::LANES);          // (-1 beyond cnt: those lanes hold -1)
+                x[u] = cs[u] >= 0 ? X4[(size_t)cs[u] * rg::LANES + t] : f4_zero();
             }
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
@@ -126,55 +108,56 @@ __device__ __forceinline__ int nmax_arg(const int64_t* __restrict__ perm, int sl
     return (slot < 0 || !perm) ? slot : (int)perm[slot];
 }
 
-__global__ __launch_bounds__(NMAX_BLOCK) void neighbor_max_group_kernel(
+__global__ __launch_bounds__(rg::BLOCK) void neighbor_max_group_kernel(
     const int32_t* __restrict__ rowptr, int n_rows, const int32_t* __restrict__ colidx, const int64_t* __restrict__ perm,
     bool skip_long, const float4* __restrict__ X4, int n_x, int n_edges, float4* __restrict__ Y4, int4* __restrict__ arg4) {
-    const int t = threadIdx.x % NMAX_GROUP;
-    const int stride = gridDim.x * NMAX_GROUPS;
-    for (long r = (long)blockIdx.x * NMAX_GROUPS + threadIdx.x / NMAX_GROUP; r < n_rows; r += stride) {
+    // (the loops of this file are written out, not rg::for_short_rows: row_groups.h says why)
+    const int t = threadIdx.x % rg::LANES;
+    const int stride = gridDim.x * rg::GROUPS;
+    for (long r = (long)blockIdx.x * rg::GROUPS + threadIdx.x / rg::LANES; r < n_rows; r += stride) {
         int start, end;
-        nmax_span_of(rowptr, (int)r, n_edges, start, end);
-        if (skip_long && end - start > NMAX_GROUP_MAX) continue;           // the block kernel's
+        rg::row_span(rowptr, (int)r, n_edges, start, end);
+        if (skip_long && end - start > rg::GROUP_MAX) continue;           // the block kernel's
         MaxState st{f4_zero(), make_int4(-1, -1, -1, -1)};
-        if (end > start) max_span<NMAX_NB>(start, end, NMAX_GROUP, t, colidx, perm, n_edges, X4, n_x, st);
-        Y4[(size_t)r * NMAX_GROUP + t] = st.v;                             // (zeros where nothing was chosen)
-        arg4[(size_t)r * NMAX_GROUP + t] =
+        if (end > start) max_span<NMAX_NB>(start, end, rg::LANES, t, colidx, perm, n_edges, X4, n_x, st);
+        Y4[(size_t)r * rg::LANES + t] = st.v;                             // (zeros where nothing was chosen)
+        arg4[(size_t)r * rg::LANES + t] =
             make_int4(nmax_arg(perm, st.s.x), nmax_arg(perm, st.s.y), nmax_arg(perm, st.s.z), nmax_arg(perm, st.s.w));
     }
 }
 
-__global__ __launch_bounds__(NMAX_BLOCK) void neighbor_max_block_kernel(
+__global__ __launch_bounds__(rg::BLOCK) void neighbor_max_block_kernel(
     const int32_t* __restrict__ rowptr, int n_rows, const int32_t* __restrict__ colidx, const int64_t* __restrict__ perm,
     const int32_t* __restrict__ long_rows, const float4* __restrict__ X4, int n_x, int n_edges, float* __restrict__ Y,
     int32_t* __restrict__ arg) {
-    __shared__ float4 s_v[NMAX_GROUPS][NMAX_GROUP];
-    __shared__ int4 s_s[NMAX_GROUPS][NMAX_GROUP];
+    __shared__ float4 s_v[rg::GROUPS][rg::LANES];
+    __shared__ int4 s_s[rg::GROUPS][rg::LANES];
     const int r = long_rows[blockIdx.x];
     if (r < 0 || r >= n_rows) return;                                      // (the whole workgroup)
     int start, end;
-    nmax_span_of(rowptr, r, n_edges, start, end);
-    const int t = threadIdx.x % NMAX_GROUP, g = threadIdx.x / NMAX_GROUP;
+    rg::row_span(rowptr, r, n_edges, start, end);
+    const int t = threadIdx.x % rg::LANES, g = threadIdx.x / rg::LANES;
     MaxState st{f4_zero(), make_int4(-1, -1, -1, -1)};
-    max_span<NMAX_NB_BLOCK>(start + g * NMAX_GROUP, end, NMAX_BLOCK, t, colidx, perm, n_edges, X4, n_x, st);
+    max_span<NMAX_NB_BLOCK>(start + g * rg::LANES, end, rg::BLOCK, t, colidx, perm, n_edges, X4, n_x, st);
     s_v[g][t] = st.v;
     s_s[g][t] = st.s;
     __syncthreads();
-    if (threadIdx.x < 4 * NMAX_GROUP) {                                    // the first wave: one column of the row per lane
+    if (threadIdx.x < 4 * rg::LANES) {                                    // the first wave: one column of the row per lane
         const float* cv = reinterpret_cast<const float*>(&s_v[0][0]) + threadIdx.x;
         const int* cs = reinterpret_cast<const int*>(&s_s[0][0]) + threadIdx.x;
         float b = 0.f;
         int bs = -1;
 #pragma unroll
-        for (int k = 0; k < NMAX_GROUPS; ++k) {
-            const float x = cv[k * 4 * NMAX_GROUP];
-            const int xs = cs[k * 4 * NMAX_GROUP];
+        for (int k = 0; k < rg::GROUPS; ++k) {
+            const float x = cv[k * 4 * rg::LANES];
+            const int xs = cs[k * 4 * rg::LANES];
             if (nmax_better(x, xs, b, bs)) {
                 b = x;
                 bs = xs;
             }
         }
-        Y[(size_t)r * (4 * NMAX_GROUP) + threadIdx.x] = b;
-        arg[(size_t)r * (4 * NMAX_GROUP) + threadIdx.x] = nmax_arg(perm, bs);
+        Y[(size_t)r * (4 * rg::LANES) + threadIdx.x] = b;
+        arg[(size_t)r * (4 * rg::LANES) + threadIdx.x] = nmax_arg(perm, bs);
     }
 }
 
@@ -185,7 +168,7 @@ __device__ __forceinline__ void nmax_row(int j, int end, const int32_t* __restri
     r = p = -1;
     if (j < 0 || j >= end) return;                              // (j < 0: base + stride + t beyond int)
     r = rowidx_t[j];
-    p = nmax_pos(perm_t, j, n_edges);
+    p = slot_pos(perm_t, j, n_edges);
     if (r < 0 || r >= n_rows || p < 0) r = -1;
 }
 
@@ -199,17 +182,17 @@ __device__ __forceinline__ void max_bwd_span(int first, int end, int stride, int
     for (int base = first; base < end; base += stride) {
         int r_next = -1, p_next = -1;
         if (end - base > stride) nmax_row(base + stride + t, end, rowidx_t, perm_t, n_edges, n_rows, r_next, p_next);
-        const int cnt = min(NMAX_GROUP, end - base);
+        const int cnt = min(rg::LANES, end - base);
         for (int k0 = 0; k0 < cnt; k0 += NB) {
             float4 gd[NB];
             int4 a[NB];
             int rs[NB], ps[NB];
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
-                rs[u] = __shfl(r, k0 + u, NMAX_GROUP);
-                ps[u] = __shfl(p, k0 + u, NMAX_GROUP);
-                a[u] = rs[u] >= 0 ? arg4[(size_t)rs[u] * NMAX_GROUP + t] : make_int4(-1, -1, -1, -1);
-                gd[u] = rs[u] >= 0 ? dY4[(size_t)rs[u] * NMAX_GROUP + t] : f4_zero();
+                rs[u] = __shfl(r, k0 + u, rg::LANES);
+                ps[u] = __shfl(p, k0 + u, rg::LANES);
+                a[u] = rs[u] >= 0 ? arg4[(size_t)rs[u] * rg::LANES + t] : make_int4(-1, -1, -1, -1);
+                gd[u] = rs[u] >= 0 ? dY4[(size_t)rs[u] * rg::LANES + t] : f4_zero();
             }
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
@@ -226,53 +209,45 @@ __device__ __forceinline__ void max_bwd_span(int first, int end, int stride, int
     }
 }
 
-__global__ __launch_bounds__(NMAX_BLOCK) void neighbor_max_bwd_group_kernel(
+__global__ __launch_bounds__(rg::BLOCK) void neighbor_max_bwd_group_kernel(
     const int32_t* __restrict__ rowptr_t, int n_cols, const int32_t* __restrict__ rowidx_t, const int64_t* __restrict__ perm_t,
     bool skip_long, int n_rows, int n_edges, const int4* __restrict__ arg4, const float4* __restrict__ dY4,
     const float4* __restrict__ base4, float4* __restrict__ dX4) {
-    const int t = threadIdx.x % NMAX_GROUP;
-    const int stride = gridDim.x * NMAX_GROUPS;
-    for (long c = (long)blockIdx.x * NMAX_GROUPS + threadIdx.x / NMAX_GROUP; c < n_cols; c += stride) {
+    const int t = threadIdx.x % rg::LANES;
+    const int stride = gridDim.x * rg::GROUPS;
+    for (long c = (long)blockIdx.x * rg::GROUPS + threadIdx.x / rg::LANES; c < n_cols; c += stride) {
         int start, end;
-        nmax_span_of(rowptr_t, (int)c, n_edges, start, end);
-        if (skip_long && end - start > NMAX_GROUP_MAX) continue;           // the block kernel's
-        float4 acc = base4 ? base4[(size_t)c * NMAX_GROUP + t] : f4_zero();
-        if (end > start) max_bwd_span<NMAX_NB>(start, end, NMAX_GROUP, t, rowidx_t, perm_t, n_edges, n_rows, arg4, dY4, acc);
-        dX4[(size_t)c * NMAX_GROUP + t] = acc;
+        rg::row_span(rowptr_t, (int)c, n_edges, start, end);
+        if (skip_long && end - start > rg::GROUP_MAX) continue;           // the block kernel's
+        float4 acc = base4 ? base4[(size_t)c * rg::LANES + t] : f4_zero();
+        if (end > start) max_bwd_span<NMAX_NB>(start, end, rg::LANES, t, rowidx_t, perm_t, n_edges, n_rows, arg4, dY4, acc);
+        dX4[(size_t)c * rg::LANES + t] = acc;
     }
 }
 
-__global__ __launch_bounds__(NMAX_BLOCK) void neighbor_max_bwd_block_kernel(
+__global__ __launch_bounds__(rg::BLOCK) void neighbor_max_bwd_block_kernel(
     const int32_t* __restrict__ rowptr_t, int n_cols, const int32_t* __restrict__ rowidx_t, const int64_t* __restrict__ perm_t,
     const int32_t* __restrict__ long_cols, int n_rows, int n_edges, const int4* __restrict__ arg4,
     const float4* __restrict__ dY4, const float* __restrict__ base, float* __restrict__ dX) {
-    __shared__ float4 s_acc[NMAX_GROUPS][NMAX_GROUP];
+    __shared__ float4 s_acc[rg::GROUPS][rg::LANES];
     const int c = long_cols[blockIdx.x];
     if (c < 0 || c >= n_cols) return;                                      // (the whole workgroup)
     int start, end;
-    nmax_span_of(rowptr_t, c, n_edges, start, end);
-    const int t = threadIdx.x % NMAX_GROUP, g = threadIdx.x / NMAX_GROUP;
+    rg::row_span(rowptr_t, c, n_edges, start, end);
+    const int t = threadIdx.x % rg::LANES, g = threadIdx.x / rg::LANES;
     float4 acc = f4_zero();
-    max_bwd_span<NMAX_NB_BLOCK_BWD>(start + g * NMAX_GROUP, end, NMAX_BLOCK, t, rowidx_t, perm_t, n_edges, n_rows, arg4, dY4, acc);
-    s_acc[g][t] = acc;
-    __syncthreads();
-    if (threadIdx.x < 4 * NMAX_GROUP) {                                    // the first wave: one column of dX[c] per lane
-        const float* col = reinterpret_cast<const float*>(&s_acc[0][0]) + threadIdx.x;
-        float y = base ? base[(size_t)c * (4 * NMAX_GROUP) + threadIdx.x] : 0.f;
-#pragma unroll
-        for (int k = 0; k < NMAX_GROUPS; ++k) y += col[k * 4 * NMAX_GROUP];
-        dX[(size_t)c * (4 * NMAX_GROUP) + threadIdx.x] = y;
-    }
+    max_bwd_span<NMAX_NB_BLOCK_BWD>(start + g * rg::LANES, end, rg::BLOCK, t, rowidx_t, perm_t, n_edges, n_rows, arg4, dY4, acc);
+    rg::store_column_sums(s_acc, g, t, acc, base, dX, c);
 }
 
 }  // namespace
 
-extern "C" int32_t mmrec_neighbor_max_group_max(void) { return NMAX_GROUP_MAX; }
+extern "C" int32_t mmrec_neighbor_max_group_max(void) { return rg::GROUP_MAX; }
 
 extern "C" int mmrec_neighbor_max_f32(const int32_t* rowptr, int32_t n_rows, const int32_t* colidx, const int64_t* perm,
                                       const int32_t* long_rows, int32_t n_long, const float* X, int64_t n_x, int32_t d,
                                       int64_t n_edges, float* Y, int32_t* arg, mmrec_stream_t stream) {
-    if (d != 4 * NMAX_GROUP) return MMREC_ERR_UNSUPPORTED;
+    if (d != 4 * rg::LANES) return MMREC_ERR_UNSUPPORTED;
     if (n_rows < 0 || n_edges < 0 || n_long < 0 || n_x < 0) return MMREC_ERR_BAD_ARG;
     if (n_rows == 0) return 0;                                             // nothing to write
     if (n_edges > INT32_MAX || n_x > INT32_MAX) return MMREC_ERR_UNSUPPORTED;
@@ -280,13 +255,17 @@ extern "C" int mmrec_neighbor_max_f32(const int32_t* rowptr, int32_t n_rows, con
     if (n_edges > 0 && (!colidx || !X)) return MMREC_ERR_BAD_ARG;
     if (n_long > 0 && !long_rows) return MMREC_ERR_BAD_ARG;
     hipStream_t s = mmrec_stream(stream);
-    const int blocks = (n_rows + NMAX_GROUPS - 1) / NMAX_GROUPS;
-    hipLaunchKernelGGL(neighbor_max_group_kernel, dim3(blocks < NMAX_MAX_BLOCKS ? blocks : NMAX_MAX_BLOCKS), dim3(NMAX_BLOCK), 0,
-                       s, rowptr, (int)n_rows, colidx, perm, n_long > 0, reinterpret_cast<const float4*>(X), (int)n_x,
-                       (int)n_edges, reinterpret_cast<float4*>(Y), reinterpret_cast<int4*>(arg));
-    if (n_long > 0)
-        hipLaunchKernelGGL(neighbor_max_block_kernel, dim3(n_long), dim3(NMAX_BLOCK), 0, s, rowptr, (int)n_rows, colidx, perm,
-                           long_rows, reinterpret_cast<const float4*>(X), (int)n_x, (int)n_edges, Y, arg);
+    const float4* X4 = reinterpret_cast<const float4*>(X);
+    rg::launch_pair(
+        n_rows, n_long,
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(neighbor_max_group_kernel, grid, dim3(rg::BLOCK), 0, s, rowptr, (int)n_rows, colidx, perm, n_long > 0,
+                               X4, (int)n_x, (int)n_edges, reinterpret_cast<float4*>(Y), reinterpret_cast<int4*>(arg));
+        },
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(neighbor_max_block_kernel, grid, dim3(rg::BLOCK), 0, s, rowptr, (int)n_rows, colidx, perm, long_rows,
+                               X4, (int)n_x, (int)n_edges, Y, arg);
+        });
     MMREC_RETURN_LAUNCH_STATUS();
 }
 
@@ -294,7 +273,7 @@ extern "C" int mmrec_neighbor_max_bwd_f32(const int32_t* rowptr_t, int32_t n_col
                                           const int64_t* perm_t, const int32_t* long_cols, int32_t n_long_t,
                                           const int32_t* arg, int64_t n_rows, const float* dY, int32_t d, int64_t n_edges,
                                           float* dX, const float* dX_base, mmrec_stream_t stream) {
-    if (d != 4 * NMAX_GROUP) return MMREC_ERR_UNSUPPORTED;
+    if (d != 4 * rg::LANES) return MMREC_ERR_UNSUPPORTED;
     if (n_cols < 0 || n_edges < 0 || n_long_t < 0 || n_rows < 0) return MMREC_ERR_BAD_ARG;
     if (n_cols == 0) return 0;                                             // nothing to write
     if (n_edges > INT32_MAX || n_rows > INT32_MAX) return MMREC_ERR_UNSUPPORTED;
@@ -302,14 +281,18 @@ extern "C" int mmrec_neighbor_max_bwd_f32(const int32_t* rowptr_t, int32_t n_col
     if (n_edges > 0 && (!rowidx_t || !arg || !dY)) return MMREC_ERR_BAD_ARG;
     if (n_long_t > 0 && !long_cols) return MMREC_ERR_BAD_ARG;
     hipStream_t s = mmrec_stream(stream);
-    const int blocks = (n_cols + NMAX_GROUPS - 1) / NMAX_GROUPS;
-    hipLaunchKernelGGL(neighbor_max_bwd_group_kernel, dim3(blocks < NMAX_MAX_BLOCKS ? blocks : NMAX_MAX_BLOCKS), dim3(NMAX_BLOCK),
-                       0, s, rowptr_t, (int)n_cols, rowidx_t, perm_t, n_long_t > 0, (int)n_rows, (int)n_edges,
-                       reinterpret_cast<const int4*>(arg), reinterpret_cast<const float4*>(dY),
-                       reinterpret_cast<const float4*>(dX_base), reinterpret_cast<float4*>(dX));
-    if (n_long_t > 0)
-        hipLaunchKernelGGL(neighbor_max_bwd_block_kernel, dim3(n_long_t), dim3(NMAX_BLOCK), 0, s, rowptr_t, (int)n_cols, rowidx_t,
-                           perm_t, long_cols, (int)n_rows, (int)n_edges, reinterpret_cast<const int4*>(arg),
-                           reinterpret_cast<const float4*>(dY), dX_base, dX);
+    const int4* arg4 = reinterpret_cast<const int4*>(arg);
+    const float4* dY4 = reinterpret_cast<const float4*>(dY);
+    rg::launch_pair(
+        n_cols, n_long_t,
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(neighbor_max_bwd_group_kernel, grid, dim3(rg::BLOCK), 0, s, rowptr_t, (int)n_cols, rowidx_t, perm_t,
+                               n_long_t > 0, (int)n_rows, (int)n_edges, arg4, dY4, reinterpret_cast<const float4*>(dX_base),
+                               reinterpret_cast<float4*>(dX));
+        },
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(neighbor_max_bwd_block_kernel, grid, dim3(rg::BLOCK), 0, s, rowptr_t, (int)n_cols, rowidx_t, perm_t,
+                               long_cols, (int)n_rows, (int)n_edges, arg4, dY4, dX_base, dX);
+        });
     MMREC_RETURN_LAUNCH_STATUS();
 }

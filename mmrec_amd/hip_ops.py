@@ -1864,6 +1864,20 @@ class DynGraph:
             return g, perm
         self.fwd, self.perm = build(rows, cols, self.n_rows, self.n_cols)
         self.bwd, self.perm_t = build(cols, rows, self.n_cols, self.n_rows)
+        self._long_rows = {}                               # by -> device list (or None) for the per-row edge ops: `side`
+
+    def side(self, by):
+        """(CsrGraph, perm, long_rows or None, n_long) of one direction, by="row" or "col", for the per-row edge ops (segment
+        softmax, edge attention, neighbour max).  The long-row list is built on the host once per DynGraph and direction and
+        checked against the row lengths (`segment_long_rows`)."""
+        if by not in ("row", "col"):
+            raise ValueError("DynGraph.side: by must be 'row' or 'col', got %r" % (by,))
+        g, perm = (self.fwd, self.perm) if by == "row" else (self.bwd, self.perm_t)
+        if by not in self._long_rows:
+            lr = segment_long_rows(g.rowptr_host)
+            self._long_rows[by] = torch.from_numpy(lr).to(g.rowptr.device) if lr.size else None
+        lr = self._long_rows[by]
+        return g, perm, lr, 0 if lr is None else lr.numel()
 
 
 class _SpMMVals(torch.autograd.Function):
@@ -2228,10 +2242,15 @@ def segment_softmax_group_max():
 def segment_long_rows(rowptr_host):
     """The rows (int32, ascending, host) of a CSR rowptr that are longer than `segment_softmax_group_max()`: the SpMM's plan
     helper at that threshold.  Checked here against the lengths: the library cannot check a device list, and a list that
-    disagrees with the kernel's constant would leave rows of the output unwritten."""
+    disagrees with the kernel's constant would leave rows of the output unwritten.  One list serves the segment softmax, the
+    edge attention and the neighbour max, so a library in which their three constants differ (MMREC_HIP_LIB may name any
+    build) is refused here rather than served a list cut at the wrong length."""
     lib = _lib.load()
     rp = np.ascontiguousarray(rowptr_host, dtype=np.int32)
     n_rows, thr = rp.size - 1, segment_softmax_group_max()
+    if not edge_attention_group_max() == neighbor_max_group_max() == thr:
+        raise _lib.MMRecHipError("group maxima of the segment softmax, the edge attention and the neighbour max differ: %d, %d, %d"
+                                 % (thr, edge_attention_group_max(), neighbor_max_group_max()))
     n_long, n_chunks = ctypes.c_int32(0), ctypes.c_int32(0)
     ptr = rp.ctypes.data_as(ctypes.c_void_p)
     _lib.check(lib.mmrec_spmm_plan_count(ptr, n_rows, thr, ctypes.byref(n_long), ctypes.byref(n_chunks)), "spmm_plan_count")
@@ -2245,18 +2264,6 @@ def segment_long_rows(rowptr_host):
     return lr
 
 
-def _softmax_side(dyn, by):
-    """(CsrGraph, perm, long_rows or None) of one direction; the long-row list is built once per DynGraph and direction"""
-    if by not in ("row", "col"):
-        raise ValueError("edge_softmax: by must be 'row' or 'col', got %r" % (by,))
-    g, perm = (dyn.fwd, dyn.perm) if by == "row" else (dyn.bwd, dyn.perm_t)
-    cache = dyn.__dict__.setdefault("_softmax_long", {})
-    if by not in cache:
-        lr = segment_long_rows(g.rowptr_host)
-        cache[by] = torch.from_numpy(lr).to(g.rowptr.device) if lr.size else None
-    return g, perm, cache[by]
-
-
 def edge_softmax_served(score, dyn):
     """True where `edge_softmax` runs the kernels: a contiguous 1-D fp32 device tensor with one entry per edge of `dyn`, and
     the `EDGE_SOFTMAX` switch on."""
@@ -2267,8 +2274,7 @@ def edge_softmax_served(score, dyn):
 class _EdgeSoftmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, score, dyn, by, eps):
-        g, perm, long_rows = _softmax_side(dyn, by)
-        n_long = 0 if long_rows is None else long_rows.numel()
+        g, perm, long_rows, n_long = dyn.side(by)
         alpha = torch.empty_like(score)
         _lib.check(_lib.load().mmrec_segment_softmax_f32(_p(g.rowptr), g.n_rows, _p(perm), _p(long_rows), n_long, _p(score),
                                                          score.numel(), eps, _p(alpha), _stream()), "segment_softmax")
@@ -2279,8 +2285,7 @@ class _EdgeSoftmax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         (alpha,) = ctx.saved_tensors
-        g, perm, long_rows = _softmax_side(ctx.dyn, ctx.by)
-        n_long = 0 if long_rows is None else long_rows.numel()
+        g, perm, long_rows, n_long = ctx.dyn.side(ctx.by)
         grad = grad.contiguous()
         ds = torch.empty_like(alpha)
         _lib.check(_lib.load().mmrec_segment_softmax_bwd_f32(_p(g.rowptr), g.n_rows, _p(perm), _p(long_rows), n_long,
@@ -2319,16 +2324,6 @@ def edge_attention_group_max():
     return int(_lib.load().mmrec_edge_attention_group_max())
 
 
-def _attention_long_rows(dyn):
-    """the long-row list (device int32, or None) of dyn's row side: built on the host once per DynGraph and checked against the
-    row lengths (`segment_long_rows`).  The attention kernel's threshold is the softmax's, so it is the softmax's cached list;
-    a library in which the two constants differ is refused rather than served a list cut at the wrong length."""
-    if edge_attention_group_max() != segment_softmax_group_max():
-        raise _lib.MMRecHipError("edge attention: group maximum %d is not the segment softmax's %d"
-                                 % (edge_attention_group_max(), segment_softmax_group_max()))
-    return _softmax_side(dyn, "row")[2]
-
-
 def edge_attention_served(Q, KV, dyn):
     """True where `edge_attention` runs the kernel: device fp32 contiguous [*, 64] tables with one row of Q per row of `dyn`
     and one row of KV per column, and the `EDGE_ATTENTION` switch on.  `Q is KV` is allowed."""
@@ -2351,20 +2346,19 @@ class _EdgeAttention(torch.autograd.Function):
         ctx.same = KV is None
         if ctx.same:
             KV = Q
-        g, n_edges = dyn.fwd, dyn.rows.numel()
-        long_rows = _attention_long_rows(dyn)
-        n_long = 0 if long_rows is None else long_rows.numel()
+        n_edges = dyn.rows.numel()
+        g, perm, long_rows, n_long = dyn.side("row")
         # every row of Y is the kernel's to write -- unless there is no edge, and then no launch
         Y = (torch.empty if n_edges else torch.zeros)(dyn.n_rows, EMB_DIM, dtype=torch.float32, device=Q.device)
         alpha = torch.empty(n_edges, dtype=torch.float32, device=Q.device)
-        _lib.check(_lib.load().mmrec_edge_attention_f32(_p(g.rowptr), g.n_rows, _p(g.colidx), _p(dyn.perm), _p(long_rows), n_long,
+        _lib.check(_lib.load().mmrec_edge_attention_f32(_p(g.rowptr), g.n_rows, _p(g.colidx), _p(perm), _p(long_rows), n_long,
                                                         _p(Q), Q.shape[0], _p(KV), KV.shape[0], EMB_DIM, n_edges, eps, _p(Y),
                                                         _p(alpha), _stream()), "edge_attention")
         ctx.dyn = dyn
         ctx.fused_backward = bool(fused_backward and EDGE_ATTENTION_BWD)
         ctx.set_materialize_grads(False)
         if ctx.fused_backward:
-            _softmax_side(dyn, "col")                           # the column side's list: host work, so here and not in backward
+            dyn.side("col")                                     # the column side's list: host work, so here and not in backward
             ctx.save_for_backward(Q, KV, alpha, Y)
         else:
             ctx.save_for_backward(Q, KV, alpha)
@@ -2379,16 +2373,16 @@ class _EdgeAttention(torch.autograd.Function):
             zq = torch.zeros_like(Q) if want_q else None
             return zq, (None if same or not want_kv else torch.zeros_like(KV)), None, None, None
         if ctx.fused_backward:                                  # one call: ds, dQ and dKV with every row gathered once
-            fwd, perm, long_rows = _softmax_side(dyn, "row")    # (both lists are cached since the forward)
-            bwd, perm_t, long_cols = _softmax_side(dyn, "col")
+            fwd, perm, long_rows, n_long = dyn.side("row")      # (both lists are cached since the forward)
+            bwd, perm_t, long_cols, n_long_t = dyn.side("col")
             dY = None if dY is None else dY.contiguous()
             dA = None if dA is None else dA.contiguous()
             ds = torch.empty_like(alpha)
             dQ = torch.empty_like(Q) if want_q else None
             dKV = torch.empty_like(KV) if want_kv else None
             _lib.check(_lib.load().mmrec_edge_attention_bwd_f32(
-                _p(fwd.rowptr), fwd.n_rows, _p(fwd.colidx), _p(perm), _p(long_rows), 0 if long_rows is None else long_rows.numel(),
-                _p(bwd.rowptr), _p(bwd.colidx), _p(perm_t), _p(long_cols), 0 if long_cols is None else long_cols.numel(),
+                _p(fwd.rowptr), fwd.n_rows, _p(fwd.colidx), _p(perm), _p(long_rows), n_long,
+                _p(bwd.rowptr), _p(bwd.colidx), _p(perm_t), _p(long_cols), n_long_t,
                 _p(Q), Q.shape[0], _p(KV), KV.shape[0], _p(ctx.saved_tensors[3]), _p(alpha), _p(dY), _p(dA), EMB_DIM,
                 alpha.numel(), _p(ds), _p(dQ), _p(dKV), _p(dQ) if same else None, _stream()), "edge_attention_bwd")
             return (dKV if same else dQ), (None if same else dKV), None, None, None
@@ -2399,8 +2393,7 @@ class _EdgeAttention(torch.autograd.Function):
             g = _edge_dot_fwd(dY, KV, dyn.rows, dyn.cols)
         if dA is not None:
             g = dA.contiguous() if g is None else g + dA
-        fwd, perm, long_rows = _softmax_side(dyn, "row")
-        n_long = 0 if long_rows is None else long_rows.numel()
+        fwd, perm, long_rows, n_long = dyn.side("row")
         ds = torch.empty_like(alpha)
         _lib.check(_lib.load().mmrec_segment_softmax_bwd_f32(_p(fwd.rowptr), fwd.n_rows, _p(perm), _p(long_rows), n_long,
                                                              _p(alpha), _p(g), alpha.numel(), _p(ds), _stream()),
@@ -2454,15 +2447,6 @@ def neighbor_max_group_max():
     return int(_lib.load().mmrec_neighbor_max_group_max())
 
 
-def _neighbor_max_side(dyn, by):
-    """`_softmax_side` for this op: its threshold is the softmax's, so it is the softmax's cached list; a library in which the
-    two constants differ is refused rather than served a list cut at the wrong length."""
-    if neighbor_max_group_max() != segment_softmax_group_max():
-        raise _lib.MMRecHipError("neighbor max: group maximum %d is not the segment softmax's %d"
-                                 % (neighbor_max_group_max(), segment_softmax_group_max()))
-    return _softmax_side(dyn, by)
-
-
 def neighbor_max_torch(X, rows, cols, n_rows):
     """Y[r][c] = max over the edges e with rows[e] == r of X[cols[e]][c], and arg [n_rows, d] (int32) = the edge chosen, by the
     kernel's SELECTION RULE: the first edge (lowest position among the row's edges) whose value is NaN; without a NaN the
@@ -2495,20 +2479,20 @@ def neighbor_max_served(X, dyn):
     """True where `neighbor_max` runs the kernels: a device fp32 contiguous [dyn.n_cols, 64] table over a `DynGraph` that
     holds both CSR forms, and the `NEIGHBOR_MAX` switch on."""
     return bool(NEIGHBOR_MAX and isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and
-                X.shape[1] == EMB_DIM and X.is_contiguous() and X.shape[0] == dyn.n_cols and hasattr(dyn, "fwd"))
+                X.shape[1] == EMB_DIM and X.is_contiguous() and X.shape[0] == dyn.n_cols and hasattr(dyn, "side"))
 
 
 class _NeighborMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, dyn):
-        g, perm, long_rows = _neighbor_max_side(dyn, "row")
-        _neighbor_max_side(dyn, "col")                          # the column side's list: host work, so here and not in backward
+        g, perm, long_rows, n_long = dyn.side("row")
+        dyn.side("col")                                         # the column side's list: host work, so here and not in backward
         n_edges = dyn.rows.numel()
         Y = torch.empty(dyn.n_rows, EMB_DIM, dtype=torch.float32, device=X.device)
         arg = torch.empty(dyn.n_rows, EMB_DIM, dtype=torch.int32, device=X.device)
         _lib.check(_lib.load().mmrec_neighbor_max_f32(_p(g.rowptr), g.n_rows, _p(g.colidx), _p(perm), _p(long_rows),
-                                                      0 if long_rows is None else long_rows.numel(), _p(X), X.shape[0], EMB_DIM,
-                                                      n_edges, _p(Y), _p(arg), _stream()), "neighbor_max")
+                                                      n_long, _p(X), X.shape[0], EMB_DIM, n_edges, _p(Y), _p(arg), _stream()),
+                   "neighbor_max")
         ctx.dyn = dyn
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(arg)
@@ -2521,12 +2505,12 @@ class _NeighborMax(torch.autograd.Function):
             return None, None
         (arg,) = ctx.saved_tensors
         dyn = ctx.dyn
-        g, perm_t, long_cols = _neighbor_max_side(dyn, "col")   # (cached since the forward)
+        g, perm_t, long_cols, n_long_t = dyn.side("col")        # (cached since the forward)
         dY = dY.contiguous()
         dX = torch.empty(dyn.n_cols, EMB_DIM, dtype=torch.float32, device=dY.device)
         _lib.check(_lib.load().mmrec_neighbor_max_bwd_f32(_p(g.rowptr), g.n_rows, _p(g.colidx), _p(perm_t), _p(long_cols),
-                                                          0 if long_cols is None else long_cols.numel(), _p(arg), dyn.n_rows,
-                                                          _p(dY), EMB_DIM, dyn.rows.numel(), _p(dX), None, _stream()),
+                                                          n_long_t, _p(arg), dyn.n_rows, _p(dY), EMB_DIM, dyn.rows.numel(), _p(dX),
+                                                          None, _stream()),
                    "neighbor_max_bwd")
         return dX, None
 

@@ -38,6 +38,26 @@ def test_header_symbols_exported_and_typed(lib):
     assert b"bad argument" in lib.mmrec_error_string(10001)
 
 
+def test_row_group_ops_share_one_threshold(lib):
+    """one long-row list per CSR serves the segment softmax, the edge attention and the neighbour max"""
+    assert (lib.mmrec_segment_softmax_group_max() == lib.mmrec_edge_attention_group_max()
+            == lib.mmrec_neighbor_max_group_max())
+
+
+def test_every_included_header_is_a_build_dependency():
+    """an edit of any header a source includes must recompile: build()'s dependency set holds them all"""
+    from mmrec_amd import build
+    deps = {os.path.basename(h) for h in build.header_deps()}
+    csrc = os.path.join(ROOT, "mmrec_amd", "csrc")
+    included = set()
+    for name in os.listdir(csrc):
+        if name.endswith((".hip", ".h")):
+            included |= {os.path.basename(h) for h in re.findall(r'#include\s+"([^"]+\.h)"', open(os.path.join(csrc, name)).read())}
+    assert "common.h" in included and "mmrec_hip.h" in included
+    assert included <= deps, "not a build dependency: %s" % sorted(included - deps)
+    assert all(os.path.exists(h) for h in build.header_deps())
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", "/nonexistent/libmmrec_hip.so")

@@ -818,8 +818,14 @@ int mmrec_coo_to_csr(const int32_t* rows, const int32_t* cols, const float* vals
 /* f1  one uniform negative per sample from cand_items[n_cand] (train-seen items), rejected while it
  * is in the user's training history (CSR hist_rowptr/hist_col, item ids sorted inside a row).
  * replaces: TrainDataLoader._sample_neg_ids utils/dataloader.py:267-275 (python `random` loop).
- * Counter-based RNG (splitmix64 of seed, counter, sample index): reproducible, but not the host
- * stream -- the host sampler remains the bit-exact parity mode.  At most 4096 draws per sample. */
+ * Counter-based RNG: reproducible, but not the host stream -- the host sampler remains the bit-exact
+ * parity mode.  With mix64 = splitmix64's output function and G = 0x9E3779B97F4A7C15, sample b starts
+ * from the state s = mix64(mix64(mix64(seed + G) + counter) + b); draw t = 1, 2, ... is mix64(s + t G), its
+ * high 32 bits r select cand_items[(r * n_cand) >> 32].  At most 4096 draws per sample: a user whose
+ * history holds every candidate gets the item of the 4096th draw.  (The three mixing rounds replace
+ * s = seed ^ (counter C + b G), under which a small seed -- 0 is the loader's default -- made sample
+ * b + 1's draws repeat sample b's, one draw late.  The ids for a given (seed, counter) therefore
+ * differ from earlier builds of ABI 16; the stream was never part of the ABI.) */
 int mmrec_sample_negatives_i64(const int64_t* users, int32_t batch, const int32_t* hist_rowptr,
                                const int32_t* hist_col, const int32_t* cand_items, int32_t n_cand,
                                uint64_t seed, uint64_t counter, int64_t* out_neg,
@@ -830,6 +836,8 @@ int mmrec_sample_negatives_i64(const int64_t* users, int32_t batch, const int32_
  * discount[j] = 1/log2(j+2), idcg_cum[j] = cumulative sum of discount (host-computed doubles, k
  * entries).  Per-user sums run sequentially in the order of numpy's cumsum: out_per_user[u][m][t]
  * (m: 0 recall, 1 ndcg, 2 precision, 3 map) is bit-identical to the reference's per-user value.
+ * A user without ground truth (an empty row) gets what the reference's formulas give there: recall
+ * NaN (0 / 0), and ndcg = 0 / idcg_cum[k-1], precision = 0 / (j + 1) and map = 0 / k, all 0.0.
  * hit_out [n_users, k] uint8 may be NULL. */
 int mmrec_topk_metrics_f64(const int64_t* topk_idx, int32_t n_users, int32_t k,
                            const int32_t* gt_rowptr, const int32_t* gt_col, const double* discount,

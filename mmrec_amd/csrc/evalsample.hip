@@ -5,15 +5,21 @@
 //      topk_evaluator.py:88-93 and the per-user part of metrics.py:12-105)
 // Integer / index work: exact.  The sampler uses its own counter-based RNG (splitmix64), so ids match
 // the host sampler statistically, not stream for stream (the host sampler stays the parity mode).
+// A sample's first state is mix64 applied three times, to the seed, then with the counter, then with the
+// sample index added (include/mmrec_hip.h): adding b times splitmix64's own increment to the state, as
+// this file once did, made sample b + 1's draw t equal sample b's draw t + 1 whenever the seed was 0.
 #include "common.h"
 
 namespace {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t& s) {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64's output function: a bijection
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t& s) {
+    return mix64(s += 0x9E3779B97F4A7C15ull);
 }
 
 __device__ __forceinline__ bool row_contains(const int32_t* __restrict__ col, int lo, int hi, int x) {
@@ -31,7 +37,8 @@ __global__ __launch_bounds__(256) void sample_negatives_kernel(
     uint64_t counter, int64_t* __restrict__ out) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= batch) return;
-    uint64_t s = seed ^ (counter * 0xD1B54A32D192ED03ull + (uint64_t)b * 0x9E3779B97F4A7C15ull);
+    // one mixing round per argument: neither a seed, nor a counter, nor b shifts one sample's stream along another's
+    uint64_t s = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15ull) + counter) + (uint64_t)b);
     const int u = (int)users[b];
     const int lo = hist_rowptr[u], hi = hist_rowptr[u + 1];
     int item = cand[0];
@@ -65,12 +72,15 @@ __global__ __launch_bounds__(256) void topk_metrics_kernel(
         sum_pre += (cum / (double)(j + 1)) * (hit ? 1.0 : 0.0);
         while (t < n_ks && ks[t] == j + 1) {
             const int cap = min(pos_len, k);                    // metrics.py:45-48,83-84
-            const int held = min(j, cap - 1);
+            // no ground truth (cap == 0): the reference's slices idcg[row, 0:] = idcg[row, -1] and ranges[0:] = ranges[-1]
+            // hold the LAST entry, so ndcg and map are 0 / idcg_cum[k-1] and 0 / k, and recall is 0 / 0
+            const int held = cap > 0 ? min(j, cap - 1) : k - 1;
+            const int map_div = cap > 0 ? min(j + 1, cap) : k;
             double* o = out + ((size_t)u * 4) * n_ks + t;
             o[0 * n_ks] = cum / (double)pos_len;
             o[1 * n_ks] = dcg / idcg_cum[held];
             o[2 * n_ks] = cum / (double)(j + 1);
-            o[3 * n_ks] = sum_pre / (double)min(j + 1, cap);
+            o[3 * n_ks] = sum_pre / (double)map_div;
             ++t;
         }
     }

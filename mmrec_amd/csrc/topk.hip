@@ -25,8 +25,10 @@
 //   threatens to overflow is bitonic-sorted, cut to k and the threshold raised to its k-th score --
 //   nothing that can be in the top-k is ever dropped.  Candidates are split over gridDim.y waves per
 //   query block; a rank-counting merge kernel turns the per-split lists into the final sorted top-k.
-//   (For kd == 64 the fused form also had a first MFMA pass for per-group maxima -> a lower bound of
-//   the k-th score; it is kept, behind MMREC_TOPK_FUSED_ONLY, as the measured alternative.)
+//   The fused form also serves EVERY kd above 2,097,152 candidates (nothing is materialised there, topk_plan).  For
+//   kd == 64 it then runs as TWO passes: a first MFMA pass for per-group maxima -> the k-th largest of them is a lower
+//   bound of the k-th score (score_groupmax_kernel, kth_largest_kernel), then score_topk_kernel<true, TK_CAPH2>.  Below
+//   that size the two-pass form is reached only with MMREC_TOPK_FUSED_ONLY (the measured alternative).
 #include "mfma_stream.h"
 #include "topk_sort.h"
 #include "topk_filter.h"

@@ -1278,7 +1278,9 @@ def test_topk_eval_shape_with_mask(ops, dev):
 
 @pytest.mark.parametrize("nq,nc,k", [(70, 5000, 50), (40, 40000, 20), (33, 3300, 64)])
 def test_topk_two_pass_and_split(ops, dev, nq, nc, k):
-    """kd = 64 and nc >= 64k candidates: group-max lower bound pass + candidate splits + merge."""
+    """kd = 64 with the best candidates masked.  (The name is historical: the two-pass kernels and the candidate splits now run
+    above 2,097,152 candidates only.  Today (70, 5000) and (40, 40000) go through the fp16 filter and (33, 3300) through the
+    materialised block path; tests/test_topk_fp32_fuzz_gpu.py covers the two-pass kernels, the splits and the merge.)"""
     rng = np.random.default_rng(nc)
     Q = rng.standard_normal((nq, 64)).astype(np.float32) * 0.3
     C = rng.standard_normal((nc, 64)).astype(np.float32) * 0.3
@@ -1294,8 +1296,10 @@ def test_topk_two_pass_and_split(ops, dev, nq, nc, k):
 
 
 def test_topk_materialised_blocks_and_heavy_masks(ops, dev):
-    """kd = 64 path at a size that needs two score blocks; one user masks 600 items (more than the
-    128 - k groups the lower bound can absorb: threshold-free fallback), one masks its whole top-300."""
+    """kd = 64 at 17000 x 5000: one user masks 600 items (more than the groups the lower bound can absorb: threshold-free
+    fallback), one masks its whole top-300.  (Today this shape is served by the fp16 filter; with MMREC_TOPK_NO_FILTER its
+    340 MB of scores are ONE block of the materialised path, whose limit is 8 GB.  Two score blocks:
+    tests/test_topk_fp32_fuzz_gpu.py::test_two_query_blocks_equal_two_calls.)"""
     rng = np.random.default_rng(7)
     nq, nc, k = 17000, 5000, 50
     Q = rng.standard_normal((nq, 64)).astype(np.float32) * 0.3

@@ -683,6 +683,63 @@ int mmrec_spectrum_bwd_f32(const float* x, const float* y, const float* w_img, c
                            const float* g_img, const float* g_txt, const float* g_fus, int64_t n, int32_t d, float* dx, float* dy,
                            float* dw_img, float* dw_txt, float* dw_fus, void* workspace, mmrec_stream_t stream);
 
+/* MGCN's behaviour-aware fuser over [n, 64] tables: modality attention, two preference gates and the mix, with its backward.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: softmax(cat(query_common(image), query_common(text))), the weighted common part, the two sigmoid gates of the
+ *           content, the three-way mean and content + side -- mgcn.py:188-203 -- and autograd's mirror of it.
+ * Served: d == 64, n <= 2^30, fp32 row-major; anything else: MMREC_ERR_UNSUPPORTED, checked first.
+ *
+ * V (image), T (text), C (content) [n, 64];  Wq, Wv, Wt [64][64] as torch's [out][in];  bq, q, bv, bt [64].  Per row:
+ *   zV = V Wq^T + bq, hV = tanh(zV), sV = <hV, q>   (zT, hT, sT from T with the same Wq, bq, q)
+ *   mx = max(sV, sT), aV = e^(sV - mx) / (e^(sV - mx) + e^(sT - mx)), aT likewise;   m = aV V + aT T
+ *   pV = sigmoid(C Wv^T + bv), pT = sigmoid(C Wt^T + bt);   side = (pV (V - m) + pT (T - m) + m) / 3;   out = C + side
+ *
+ * THE PLAN.  One workgroup per block of mmrec_modal_fusion_rows_per_block(n) consecutive rows (64 ceil(n / 16,384): a multiple
+ * of 64, a function of n alone, at most 256 blocks), walked in tiles of 64 rows that stay in LDS with the three matrices.  All
+ * arithmetic is fp32; every operation named below is ONE rounding (an fma is one), in this order (where a product feeds only an
+ * addition the compiler may contract the two into one fma: a rounding fewer, never one more):
+ *   z, u     a chain of 64 fma over the input column k ascending, started at the bias.
+ *   tanh     qe = expf(-2 |z|), h = copysign((1 - qe) / (1 + qe), z);   sigmoid: qe = expf(-|z|), p = (z >= 0 ? 1 : qe) / (1 + qe).
+ *            The argument of expf is exact and <= 0; h is exactly +-1 and p exactly 1 or 0 once qe underflows to 0: never a NaN.
+ *   s        over the columns c = l, l + 16, l + 32, l + 48 (l = 0 .. 15): s = fma(h_c, q_c, s) from 0, then the 16 partial sums
+ *            by a butterfly (xor 8, 4, 2, 1): 4 + 4 roundings.
+ *   a        eV = expf(sV - mx), eT = expf(sT - mx), den = eV + eT, aV = eV / den, aT = eT / den.
+ *   mix      m = fma(aT, T, aV V), xV = V - m, xT = T - m, side = fma(pT, xT, fma(pV, xV, m)) / 3, out = C + side.
+ * mmrec_modal_fusion_fwd_f32: ONE launch; V, T, C read once, side and out written once.
+ * mmrec_modal_fusion_bwd_f32: given g_side, g_out [n, 64], each of which may be NULL (zeros).  Every intermediate above is
+ *   RECOMPUTED from V, T, C and the weights: the state between the two calls is the operands.  Then, per element,
+ *   G = g_side + g_out, G3 = G / 3, dm = G3 ((1 - pV) - pT), dpV = G3 xV, dpT = G3 xT;
+ *   dot = fma(dm_c, V_c - T_c, dot) over the columns and butterfly of s;   dsV = (aV aT) dot, dsT = -dsV;
+ *   dzV = (dsV q) fma(-hV, hV, 1), dzT = (dsT q) fma(-hT, hT, 1);   duV = dpV (pV (1 - pV)), duT = dpT (pT (1 - pT));
+ *   dV = a chain of 64 fma of dzV Wq over the output column o ascending, started at fma(aV, dm, G3 pV);   dT alike;
+ *   dC = the chain of duV Wv started at g_out (0 if NULL), continued by the chain of duT Wt: 128 fma.
+ *   Weight gradients, per block: dWq[o][k] is ONE fma chain from 0 over the block's rows, per tile the 64 terms dzV[r][o] V[r][k]
+ *   (r ascending), then the 64 terms dzT[r][o] T[r][k]: 2 rows_per_block roundings;  dWv, dWt alike from duV, duT and C:
+ *   rows_per_block.  dbq (terms dzV + dzT), dbv (duV), dbt (duT), dq (fma(dsT, hT, dsV hV)): the rows 4 g .. 4 g + 3 of each
+ *   tile are added in order onto one sum per group g of a tile's 16 (rows_per_block / 16 additions), then the 16 groups in order
+ *   from 0 (16).  The main pass leaves one partial of 3 (64 64 + 64) + 64 = 12,544 floats per block in the workspace
+ *   ([dWq][dWv][dWt][dbq][dbv][dbt][dq]); the finish (a second launch, NOT made where no weight gradient is wanted) adds, per
+ *   output, the blocks j, j + 4, j + 8, ... in order from 0 for j = 0 .. 3 and then the four sums in order:
+ *   ceil(blocks / 4) + 3 roundings.
+ *   Any of the ten outputs may be NULL (not computed).  A wanted gradient with both g NULL is written as zeros.
+ * NO ATOMICS, every order fixed by n alone: two calls on the same inputs give the same bits.
+ * workspace: mmrec_modal_fusion_workspace_bytes(n) bytes (16-byte aligned), 12,544 floats per block (12.8 MB at most); 0 for
+ * n < 0 or n > 2^30; needed only where a weight gradient is wanted.  Outputs must not alias inputs.
+ * d != 64 or n > 2^30: MMREC_ERR_UNSUPPORTED; n < 0: MMREC_ERR_BAD_ARG; n == 0: 0, no launch; a NULL operand or forward output,
+ * or a NULL workspace where a weight gradient is wanted: MMREC_ERR_BAD_ARG -- in this order, before any pointer is followed.
+ * No synchronisation, no allocation, no data-dependent launch shape, capture-safe (the first call on a device raises the
+ * kernels' LDS limit: make one call before capturing). */
+int32_t mmrec_modal_fusion_rows_per_block(int64_t n);
+size_t mmrec_modal_fusion_workspace_bytes(int64_t n);
+int mmrec_modal_fusion_fwd_f32(const float* V, const float* T, const float* C, const float* Wq, const float* bq, const float* q,
+                               const float* Wv, const float* bv, const float* Wt, const float* bt, int64_t n, int32_t d,
+                               float* side, float* out, mmrec_stream_t stream);
+int mmrec_modal_fusion_bwd_f32(const float* V, const float* T, const float* C, const float* Wq, const float* bq, const float* q,
+                               const float* Wv, const float* bv, const float* Wt, const float* bt, const float* g_side,
+                               const float* g_out, int64_t n, int32_t d, float* dV, float* dT, float* dC, float* dWq, float* dbq,
+                               float* dq, float* dWv, float* dbv, float* dWt, float* dbt, void* workspace,
+                               mmrec_stream_t stream);
+
 /* Top-k of a mix of three row softmaxes against three whole tables, never storing a [B, N] block: DAMRS's pseudo-labels.
  * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
  * replaces: topk(p_a + p_b + 2 p_m, 10) with p = softmax(normalize(h[ids]) @ normalize(h).T, dim=1) for each of three

@@ -1,0 +1,108 @@
+// [64 rows] x [64, 64] products on a 256-thread workgroup, fp32 VALU fma, both operands in LDS: the stage of the row-wise fusers
+// (modal_fusion.hip; written to be shared with the next one of the family).
+//
+// Every tile and every matrix is 64 x 64 floats with rows of T64_LD = 68 floats (float4 aligned, and 17 sixteen-byte slots: the
+// 16 lanes of a read that walk 16 rows hit 16 different slots).  Thread (rg, sg) = (tid / 16, tid % 16) always owns the tile
+// rows 4 rg .. 4 rg + 3.  Two forms, named after the BLAS letters of their second operand:
+//   t64_stage_nt  out[r][c] += sum over s of A[r][s] B[c][s]     the thread's columns are c = sg + 16 j  (j = 0 .. 3): layout L1
+//   t64_stage_nn  out[r][c] += sum over s of T[s][r] M[s][c]     the thread's columns are c = 4 sg + j   (j = 0 .. 3): layout L0
+// In both the summed index s ASCENDS and every term is one fmaf onto the accumulator the caller passes in (a bias, another
+// stage's result, or zeros): an output meets 64 roundings per stage, nothing else.
+#pragma once
+#include "common.h"
+
+constexpr int T64 = 64;
+constexpr int T64_LD = 68;
+constexpr int T64_FLOATS = T64 * T64_LD;
+constexpr int T64_BLOCK = 256;
+
+// a row-major [64][64] matrix of global memory into an LDS image with T64_LD rows (visible after the caller's next barrier)
+__device__ __forceinline__ void t64_matrix(float* __restrict__ L, const float* __restrict__ g) {
+    for (int e = threadIdx.x; e < T64 * T64 / 4; e += T64_BLOCK) {
+        const int r = e / 16, c = 4 * (e % 16);
+        *reinterpret_cast<float4*>(L + r * T64_LD + c) = *reinterpret_cast<const float4*>(g + r * T64 + c);
+    }
+}
+
+// rows row0 .. row0 + 63 of a [n, 64] table into a row-major tile; rows past n, and a NULL table, read as zeros
+__device__ __forceinline__ void t64_load(float* __restrict__ R, const float* __restrict__ g, long row0, long n, int rg, int sg) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long r = row0 + 4 * rg + i;
+        *reinterpret_cast<float4*>(R + (4 * rg + i) * T64_LD + 4 * sg) =
+            (g && r < n) ? *reinterpret_cast<const float4*>(g + (size_t)r * T64 + 4 * sg) : f4_zero();
+    }
+}
+
+// layout L0 (rows 4 rg + i, columns 4 sg .. + 3) to a [n, 64] table; rows past n are not stored
+__device__ __forceinline__ void t64_store(float* __restrict__ g, long row0, long n, int rg, int sg, const float4 (&v)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long r = row0 + 4 * rg + i;
+        if (r < n) *reinterpret_cast<float4*>(g + (size_t)r * T64 + 4 * sg) = v[i];
+    }
+}
+
+// acc[i][j] += sum_s A[4 rg + i][s] B[sg + 16 j][s], s ascending
+__device__ __forceinline__ void t64_stage_nt(const float* __restrict__ A, const float* __restrict__ B, int rg, int sg,
+                                             float (&acc)[4][4]) {
+    const float* __restrict__ a = A + 4 * rg * T64_LD;
+    const float* __restrict__ b = B + sg * T64_LD;
+#pragma unroll 2
+    for (int s = 0; s < T64; s += 4) {
+        float4 av[4], bv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = *reinterpret_cast<const float4*>(a + i * T64_LD + s);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bv[j] = *reinterpret_cast<const float4*>(b + 16 * j * T64_LD + s);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float c = acc[i][j];
+                c = fmaf(av[i].x, bv[j].x, c);
+                c = fmaf(av[i].y, bv[j].y, c);
+                c = fmaf(av[i].z, bv[j].z, c);
+                c = fmaf(av[i].w, bv[j].w, c);
+                acc[i][j] = c;
+            }
+    }
+}
+
+// acc[i] (columns 4 sg .. + 3) += sum_s T[s][4 rg + i] M[s][4 sg .. + 3], s ascending
+__device__ __forceinline__ void t64_stage_nn(const float* __restrict__ T, const float* __restrict__ M, int rg, int sg,
+                                             float4 (&acc)[4]) {
+#pragma unroll 8
+    for (int s = 0; s < T64; ++s) {
+        const float4 t = *reinterpret_cast<const float4*>(T + s * T64_LD + 4 * rg);
+        const float4 m = *reinterpret_cast<const float4*>(M + s * T64_LD + 4 * sg);
+        acc[0] = f4_fma(t.x, m, acc[0]);
+        acc[1] = f4_fma(t.y, m, acc[1]);
+        acc[2] = f4_fma(t.z, m, acc[2]);
+        acc[3] = f4_fma(t.w, m, acc[3]);
+    }
+}
+
+// layout L1 values (rows 4 rg + i, columns sg + 16 j) into a row-major tile R and, where Tt is given, its transpose
+__device__ __forceinline__ void t64_put(float* __restrict__ R, float* __restrict__ Tt, int rg, int sg, const float (&v)[4][4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = sg + 16 * j;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) R[(4 * rg + i) * T64_LD + c] = v[i][j];
+        if (Tt) *reinterpret_cast<float4*>(Tt + c * T64_LD + 4 * rg) = make_float4(v[0][j], v[1][j], v[2][j], v[3][j]);
+    }
+}
+
+// more LDS than a kernel gets by default: asked for once per device, outside any launch
+static inline int t64_allow_lds(const void* kernel, size_t bytes, bool* done) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    if (dev < 0 || dev >= 64 || !done[dev]) {
+        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return (int)e;
+        if (dev >= 0 && dev < 64) done[dev] = true;
+    }
+    return 0;
+}

@@ -3015,6 +3015,91 @@ def spectrum_fusion(image, text, w_img, w_txt, w_fus):
 
 
 # ------------------------------------------------------------------------------------------------
+# MGCN's behaviour-aware fuser (csrc/modal_fusion.hip): modality attention, two preference gates, the mix
+# ------------------------------------------------------------------------------------------------
+MODAL_FUSION = True   # False: every modal_fusion call is `modal_fusion_torch` (A/B runs)
+
+
+def modal_fusion_rows_per_block(n):
+    """rows of a table of n rows that one workgroup of the modal fusion kernels walks (the library's plan)"""
+    return int(_lib.load().mmrec_modal_fusion_rows_per_block(int(n)))
+
+
+def modal_fusion_torch(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
+    """MGCN.forward's fuser (models/mgcn.py, the `fused_fusion` key off) as a function of its ten operands: the same operations
+    in the same order -> (side, out).  The composition `modal_fusion` falls back to."""
+    def query(x):
+        return torch.nn.functional.linear(torch.tanh(linear(x.contiguous(), Wq, bq)), q)
+
+    def gate(W, b):
+        return torch.sigmoid(linear(C.contiguous(), W, b))
+    w = torch.softmax(torch.cat([query(V), query(T)], dim=-1), dim=-1)
+    common = w[:, 0].unsqueeze(1) * V + w[:, 1].unsqueeze(1) * T
+    sep_image = gate(Wv, bv) * (V - common)
+    sep_text = gate(Wt, bt) * (T - common)
+    side = (sep_image + sep_text + common) / 3
+    return side, C + side
+
+
+def modal_fusion_served(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
+    """True where `modal_fusion` runs the kernels: device fp32 contiguous [n, 64] tables of one shape, 1 <= n <= 2^30, device
+    fp32 contiguous [64, 64] matrices, [64] biases and a [1, 64] q, the `MODAL_FUSION` switch on."""
+    def ok(t, shape=None):
+        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                    (shape is None or tuple(t.shape) == shape))
+
+    def table(t):
+        return ok(t) and t.dim() == 2 and t.shape[1] == EMB_DIM and 1 <= t.shape[0] <= (1 << 30)
+    if not (MODAL_FUSION and table(V) and table(T) and table(C) and V.shape == T.shape == C.shape):
+        return False
+    return bool(all(ok(w, (EMB_DIM, EMB_DIM)) for w in (Wq, Wv, Wt)) and all(ok(b, (EMB_DIM,)) for b in (bq, bv, bt)) and
+                ok(q, (1, EMB_DIM)) and all(t.device == V.device for t in (T, C, Wq, bq, q, Wv, bv, Wt, bt)))
+
+
+class _ModalFusion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, *ops):
+        V = ops[0]
+        side, out = torch.empty_like(V), torch.empty_like(V)
+        _lib.check(_lib.load().mmrec_modal_fusion_fwd_f32(*[_p(t) for t in ops], V.shape[0], EMB_DIM, _p(side), _p(out),
+                                                          _stream()), "modal_fusion_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*ops)                                  # every intermediate is recomputed: nothing else is kept
+        return side, out
+
+    @staticmethod
+    def backward(ctx, g_side, g_out):
+        ops = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        if not any(want) or (g_side is None and g_out is None):
+            return (None,) * 10
+        lib = _lib.load()
+        n = ops[0].shape[0]
+        gs = [None if g is None else g.contiguous() for g in (g_side, g_out)]
+        grads = [torch.empty_like(t) if w else None for t, w in zip(ops, want)]
+        ws = _ws(lib.mmrec_modal_fusion_workspace_bytes(n), ops[0].device) if any(want[3:]) else None
+        _lib.check(lib.mmrec_modal_fusion_bwd_f32(*[_p(t) for t in ops], _p(gs[0]), _p(gs[1]), n, EMB_DIM,
+                                                  *[_p(g) for g in grads], _p(ws), _stream()), "modal_fusion_bwd")
+        return tuple(grads)
+
+
+def modal_fusion(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
+    """MGCN's behaviour-aware fuser (mgcn.py:188-203) -> (side, out), each [n, 64]:
+    a = softmax(<tanh(V Wq^T + bq), q>, <tanh(T Wq^T + bq), q>), m = a_0 V + a_1 T, side = (sigmoid(C Wv^T + bv) (V - m) +
+    sigmoid(C Wt^T + bt) (T - m) + m) / 3, out = C + side; V, T, C [n, 64] (image, text, content), the matrices [64, 64] as
+    nn.Linear keeps them, q = query_common[2].weight [1, 64].  Differentiable in all ten operands.
+    Served by the kernels (`modal_fusion_served`): one launch forward, two backward (the main pass and the finish that adds the
+    blocks' weight-gradient partials in a fixed order); the three tables read once, the two outputs written once, every
+    intermediate kept in LDS and RECOMPUTED in the backward, so the state between the calls is the ten operands.  An operand
+    that needs no gradient is not computed.  No atomics: the same bits every call, so `DETERMINISTIC` changes nothing.
+    EVERY OTHER CASE (CPU tensors, a width other than 64, other dtypes, non-contiguous operands, an empty table, the switch
+    off) is `modal_fusion_torch` with stock autograd."""
+    if modal_fusion_served(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
+        return _ModalFusion.apply(V, T, C, Wq, bq, q, Wv, bv, Wt, bt)
+    return modal_fusion_torch(V, T, C, Wq, bq, q, Wv, bv, Wt, bt)
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

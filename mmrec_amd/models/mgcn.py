@@ -10,8 +10,12 @@ loss   : fused BPR + fused gather-norm regulariser + two fused in-batch InfoNCE 
          (`hip_ops.infonce`: the [B, B] logits are never materialised, forward or backward)
 eval   : fused score + mask + top-K
 The 64 -> 64 gate / attention layers run on the same fp32 MFMA projection kernels (the library's
-skinny dW GEMMs measured 107-150 us each, 30 % of the step); only the 64 -> 1 attention head is a
-library matvec.
+skinny dW GEMMs measured 107-150 us each, 30 % of the step).  The behaviour-aware fuser after the
+graphs (mgcn.py:188-203) is, by default, a composition over all users + items rows: four of those
+projections, tanh / sigmoid, the two 64 -> 1 attention heads as library matvecs, a two-column
+softmax and a dozen element-wise launches.  With the config key `fused_fusion: True` (absent /
+False: that path, untouched) it is one `hip_ops.modal_fusion` call (csrc/modal_fusion.hip: one
+launch forward, two backward, no library call left in the step).
 """
 import os
 
@@ -84,6 +88,7 @@ class MGCN(FusedEvalMixin, GeneralRecommender):
         self.n_layers = config['n_layers']
         self.reg_weight = config['reg_weight']
         self.tau = 0.5
+        self.fused_fusion = bool(config['fused_fusion']) if 'fused_fusion' in config else False    # new key, default off
 
         self.interaction_matrix = dataset.inter_matrix(form='coo').astype(np.float32)
         self.norm_adj, self.R = mgcn_norm_graphs(self.interaction_matrix, self.n_users, self.n_items, self.device)
@@ -138,12 +143,17 @@ class MGCN(FusedEvalMixin, GeneralRecommender):
             text_item = hip_ops.spmm(self.text_original_adj, text_item)
         text_embeds = torch.cat([hip_ops.spmm(self.R, text_item), text_item], dim=0)
 
-        w = torch.softmax(torch.cat([self._query(image_embeds), self._query(text_embeds)], dim=-1), dim=-1)
-        common = w[:, 0].unsqueeze(1) * image_embeds + w[:, 1].unsqueeze(1) * text_embeds
-        sep_image = self._gate(self.gate_image_prefer, content) * (image_embeds - common)
-        sep_text = self._gate(self.gate_text_prefer, content) * (text_embeds - common)
-        side = (sep_image + sep_text + common) / 3
-        out = content + side
+        if self.fused_fusion:
+            qc, gv, gt = self.query_common, self.gate_image_prefer[0], self.gate_text_prefer[0]
+            side, out = hip_ops.modal_fusion(image_embeds.contiguous(), text_embeds.contiguous(), content.contiguous(),
+                                             qc[0].weight, qc[0].bias, qc[2].weight, gv.weight, gv.bias, gt.weight, gt.bias)
+        else:
+            w = torch.softmax(torch.cat([self._query(image_embeds), self._query(text_embeds)], dim=-1), dim=-1)
+            common = w[:, 0].unsqueeze(1) * image_embeds + w[:, 1].unsqueeze(1) * text_embeds
+            sep_image = self._gate(self.gate_image_prefer, content) * (image_embeds - common)
+            sep_text = self._gate(self.gate_text_prefer, content) * (text_embeds - common)
+            side = (sep_image + sep_text + common) / 3
+            out = content + side
         users, items = out[:self.n_users], out[self.n_users:]
         if train:
             return users, items, side, content

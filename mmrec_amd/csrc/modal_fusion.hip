@@ -42,11 +42,8 @@ constexpr int64_t MF_MAX_ROWS = (int64_t)1 << 30;
 
 constexpr size_t mf_lds_bytes(int tiles) { return sizeof(float) * ((size_t)(3 + tiles) * T64_FLOATS + MF_VEC); }
 
-inline int mf_rows_per_block(int64_t n) {
-    int64_t t = (n + (int64_t)T64 * MF_MAX_BLOCKS - 1) / ((int64_t)T64 * MF_MAX_BLOCKS);
-    return (int)(t < 1 ? 1 : t) * T64;
-}
-inline int mf_blocks(int64_t n) { return n <= 0 ? 0 : (int)((n + mf_rows_per_block(n) - 1) / mf_rows_per_block(n)); }
+inline int mf_rows_per_block(int64_t n) { return t64_rows_per_block(n, MF_MAX_BLOCKS); }
+inline int mf_blocks(int64_t n) { return t64_blocks(n, MF_MAX_BLOCKS); }
 
 __device__ __forceinline__ float mf_tanh(float z) {
     const float q = expf(-2.f * fabsf(z));

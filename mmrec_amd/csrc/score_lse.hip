@@ -5,13 +5,10 @@
 // pgl.py:226-231, at width 128.)  infonce.hip is the square, 64-wide, plain-FMA kernel of a B x B problem; a B x N sweep is
 // 10-100 times that work and runs on the fp32-input MFMA.
 //
-// One kernel, three modes.  A workgroup (4 waves) OWNS 128 rows of one operand -- a wave 32 of them, their fragment in
-// registers for the whole walk (lane (i, h) holds own[i][2 s + h]) -- and walks a range of 64-row tiles of the OTHER operand,
-// which reach the waves through LDS: coalesced 16-byte global loads into registers one tile ahead, stored de-interleaved
-// (even k in the first half of a row, odd k in the second, pitch d + 4 floats) so that a lane's MFMA operands of four
-// consecutive steps are ONE conflict-free 16-byte LDS read and the contraction still runs in natural k order:
+// One kernel, three modes, all the sweep of mfma_sweep.h: a workgroup (4 waves) OWNS 128 rows of one operand, their fragments
+// in registers, and walks a range of 64-row tiles of the OTHER operand, which reach the waves through LDS, de-interleaved:
 //   s(other o, own i) = fma chain over k = 0 .. d-1 of other[o][k] * own[i][k]       (v_mfma_f32_32x32x2_f32, bitwise that chain)
-// With the tile as the A operand a lane holds 16 others of ONE own row: D[other = d_row(r, lane)][own = lane & 31].
+// A lane holds 16 others of ONE own row: D[other = d_row(r, lane)][own = lane & 31].
 //   MODE 0  own = Q, other = K: per lane a running (max, rescaled sum) over its 16 scores per sub-tile, the two lanes of a row
 //           combined once at the end (h = 0 first), one (m, sum) per (column split, row); `sl_finish_kernel` combines the
 //           splits in split order:  M = max m_s,  L = sum_s l_s exp(m_s - M),  lse = M + log L.
@@ -21,41 +18,22 @@
 // into the A operand, the B operand is the tile already in LDS, the contraction runs over the tile's rows in order.
 // Grid (own tiles x splits of the other operand): partial sums per split, added in split order by `sl_reduce_kernel` (one
 // split: straight into the result).  No atomics; every sum has one fixed order, so two calls give the same bits.
-#include "mfma_stream.h"
+#include "mfma_sweep.h"
 
 namespace {
 
-constexpr int SL_OWN = 128;            // own rows per workgroup
-constexpr int SL_TILE = 64;            // other rows per LDS tile (two 32-row MFMA sub-tiles)
 constexpr int SL_FWD_WGS = 512;        // workgroups the forward grid aims at (2 per CU)
 constexpr int SL_BWD_WGS = 256;
 constexpr int SL_FWD_SPLITS_MAX = 64;
 constexpr int SL_BWD_SPLITS_MAX = 16;
 constexpr int SL_ROWS_MAX = 1 << 30;   // row indices (+ a tile) stay in int32
 
-struct SlPlan {
-    int own_tiles, oth_tiles, per, splits;     // per: tiles of the other operand per split
-};
-// a function of the two sizes only (never of data): capturable, and the same call always has the same plan
-inline SlPlan sl_plan(long n_own, long n_oth, int target, int cap) {
-    SlPlan p;
-    p.own_tiles = (int)((n_own + SL_OWN - 1) / SL_OWN);
-    p.oth_tiles = (int)((n_oth + SL_TILE - 1) / SL_TILE);
-    long want = (target + (long)(p.own_tiles > 0 ? p.own_tiles : 1) - 1) / (p.own_tiles > 0 ? p.own_tiles : 1);
-    if (want > cap) want = cap;
-    if (want > p.oth_tiles) want = p.oth_tiles;
-    if (want < 1) want = 1;
-    p.per = (int)((p.oth_tiles + want - 1) / want);
-    if (p.per < 1) p.per = 1;
-    p.splits = (p.oth_tiles + p.per - 1) / p.per;
-    return p;
-}
-inline SlPlan sl_plan_fwd(long B, long N) { return sl_plan(B, N, SL_FWD_WGS, SL_FWD_SPLITS_MAX); }
+inline SweepPlan sl_plan_fwd(long B, long N) { return sweep_plan(B, N, SL_FWD_WGS, SL_FWD_SPLITS_MAX); }
 // backward: the partial results are [splits][n_own][d]; they never exceed 4 (B + N) d floats
-inline SlPlan sl_plan_bwd(long n_own, long n_oth) {
+inline SweepPlan sl_plan_bwd(long n_own, long n_oth) {
     long cap = n_own > 0 ? 4 * (n_own + n_oth) / n_own : 1;
     if (cap > SL_BWD_SPLITS_MAX) cap = SL_BWD_SPLITS_MAX;
-    return sl_plan(n_own, n_oth, SL_BWD_WGS, (int)cap);
+    return sweep_plan(n_own, n_oth, SL_BWD_WGS, (int)cap);
 }
 
 __device__ __forceinline__ float sl_max16(const float (&a)[16]) {
@@ -71,57 +49,40 @@ __global__ __launch_bounds__(256) void sl_sweep_kernel(const float* __restrict__
                                                        int per, const float* __restrict__ lse,
                                                        const float* __restrict__ g, float* __restrict__ out0,
                                                        float* __restrict__ out1) {
-    constexpr int LD = D + 4;           // tile pitch: rows 16 B aligned, 16 consecutive rows on 64 different banks
-    constexpr int NV = D / 16;          // float4 a thread brings per tile
+    constexpr int LD = D + 4;           // tile pitch (mfma_sweep.h)
     constexpr int NC = D / 32;          // 32-column chunks of a gradient row
-    __shared__ __attribute__((aligned(16))) float T[SL_TILE * LD];
+    __shared__ __attribute__((aligned(16))) float T[SWEEP_TILE * LD];
     __shared__ float P[MODE ? 4 : 1][MODE ? 32 * 33 : 1];
-    __shared__ float Tl[MODE == 2 ? SL_TILE : 1], Tg[MODE == 2 ? SL_TILE : 1];
+    __shared__ float Tl[MODE == 2 ? SWEEP_TILE : 1], Tg[MODE == 2 ? SWEEP_TILE : 1];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, h = lane >> 5;
-    const int own0 = blockIdx.x * SL_OWN + wave * 32;
-    const int oth_tiles = (n_oth + SL_TILE - 1) / SL_TILE;
+    const int own0 = blockIdx.x * SWEEP_OWN + wave * 32;
+    const int oth_tiles = (n_oth + SWEEP_TILE - 1) / SWEEP_TILE;
     const int t_begin = blockIdx.y * per, t_end = min(t_begin + per, oth_tiles);
 
-    // own fragment: own[own0 + i][2 s + h]; rows past the end are zero
-    float qf[D / 2];
-    {
-        const int row = own0 + i;
-        const float* src = Own + (size_t)(row < n_own ? row : 0) * D + h;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s) qf[s] = row < n_own ? src[2 * s] : 0.f;
-    }
+    float qf[D / 2];                    // own[own0 + i][2 s + h]; rows past the end are zero
+    sweep_own<D>(qf, Own + (size_t)(own0 + i < n_own ? own0 + i : 0) * D, own0 + i < n_own, h);
     float own_l = 0.f, own_g = 0.f;
     if (MODE == 1 && own0 + i < n_own) {
         own_l = lse[own0 + i];
         own_g = scale * g[own0 + i];
     }
 
-    float4 pre[NV];
+    float4 pre[D / 16];
     float pre_l = 0.f, pre_g = 0.f;
     auto fetch = [&](int t) {
-        const int o0 = t * SL_TILE;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int e = tid + 256 * j, r = e / (D / 4), c4 = e % (D / 4);
-            pre[j] = ld4_guard(Oth + (size_t)(o0 + r < n_oth ? o0 + r : 0) * D + 4 * c4, o0 + r < n_oth);
-        }
-        if (MODE == 2 && tid < SL_TILE) {
+        const int o0 = t * SWEEP_TILE;
+        sweep_fetch<D>(pre, Oth, o0, n_oth, tid);
+        if (MODE == 2 && tid < SWEEP_TILE) {
             const bool ok = o0 + tid < n_oth;
             pre_l = ok ? lse[o0 + tid] : 0.f;
             pre_g = ok ? scale * g[o0 + tid] : 0.f;
         }
     };
     auto stage = [&]() {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int e = tid + 256 * j, r = e / (D / 4), c4 = e % (D / 4);
-            float* row = T + r * LD;
-            *reinterpret_cast<float2*>(row + 2 * c4) = make_float2(pre[j].x, pre[j].z);             // k = 4 c4, 4 c4 + 2
-            *reinterpret_cast<float2*>(row + D / 2 + 2 * c4) = make_float2(pre[j].y, pre[j].w);     // k = 4 c4 + 1, + 3
-        }
-        if (MODE == 2 && tid < SL_TILE) { Tl[tid] = pre_l; Tg[tid] = pre_g; }
+        sweep_stage<D>(T, pre, tid);
+        if (MODE == 2 && tid < SWEEP_TILE) { Tl[tid] = pre_l; Tg[tid] = pre_g; }
     };
 
     float m_run = -INFINITY, l_run = 0.f;          // MODE 0
@@ -135,20 +96,11 @@ __global__ __launch_bounds__(256) void sl_sweep_kernel(const float* __restrict__
         stage();
         __syncthreads();
         if (t + 1 < t_end) fetch(t + 1);           // in flight under this tile's MFMAs
-        const int o0 = t * SL_TILE;
+        const int o0 = t * SWEEP_TILE;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (o0 + 32 * u >= n_oth) break;       // uniform: nothing but padding in this sub-tile
-            f32x16 acc = {0};
-            const float* tr = T + (32 * u + i) * LD + h * (D / 2);
-#pragma unroll
-            for (int q4 = 0; q4 < D / 8; ++q4) {
-                const float4 a = *reinterpret_cast<const float4*>(tr + 4 * q4);
-                acc = mfma32(a.x, qf[4 * q4 + 0], acc);
-                acc = mfma32(a.y, qf[4 * q4 + 1], acc);
-                acc = mfma32(a.z, qf[4 * q4 + 2], acc);
-                acc = mfma32(a.w, qf[4 * q4 + 3], acc);
-            }
+            const f32x16 acc = sweep_scores<D>(T, u, i, h, qf);
             const bool partial = o0 + 32 * u + 32 > n_oth;      // uniform
             float x[16];
 #pragma unroll
@@ -175,13 +127,9 @@ __global__ __launch_bounds__(256) void sl_sweep_kernel(const float* __restrict__
                     if (partial) w = o0 + oo < n_oth ? w : 0.f;
                     pw[i * 33 + d_row(r, lane)] = w;            // [own][other]
                 }
-                // the tile is private to the wave and a wave's LDS operations complete in order: no barrier, only the
-                // compiler must keep the order
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_order();                               // P is private to the wave
                 // out[own i'][dim] += sum_c W[i'][c] tile[c][dim]: A = W[own = i][c = 2 s + h], B = tile[c = 2 s + h][32 nc + i]
-                const int bpos = (i & 1) * (D / 2) + (i >> 1);  // position of column k = 32 nc + i: + 16 nc
+                const int bpos = (i & 1) * (D / 2) + (i >> 1);  // mfma_sweep.h's position of column k = 32 nc + i: + 16 nc
 #pragma unroll
                 for (int s = 0; s < 16; ++s) {
                     const float a = pw[i * 33 + 2 * s + h];
@@ -189,9 +137,7 @@ __global__ __launch_bounds__(256) void sl_sweep_kernel(const float* __restrict__
 #pragma unroll
                     for (int c = 0; c < NC; ++c) dacc[c] = mfma32(a, brow[16 * c], dacc[c]);
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_order();
             }
         }
     }
@@ -244,7 +190,7 @@ __global__ __launch_bounds__(256) void sl_reduce_kernel(const float4* __restrict
 
 inline size_t sl_bwd_floats(long n_own, long n_oth, int d) {
     if (n_own <= 0 || n_oth <= 0) return 0;
-    const SlPlan p = sl_plan_bwd(n_own, n_oth);
+    const SweepPlan p = sl_plan_bwd(n_own, n_oth);
     return p.splits > 1 ? (size_t)p.splits * (size_t)n_own * d : 0;
 }
 
@@ -260,7 +206,7 @@ inline void sl_launch(int d, dim3 grid, hipStream_t s, const float* own, int n_o
 // one gradient: own rows x splits of the other operand, then the splits in order
 inline void sl_grad(int mode, const float* own, int n_own, const float* oth, int n_oth, int d, float scale,
                     const float* lse, const float* g, float* out, float* part, hipStream_t s) {
-    const SlPlan p = sl_plan_bwd(n_own, n_oth);
+    const SweepPlan p = sl_plan_bwd(n_own, n_oth);
     float* dst = p.splits > 1 ? part : out;
     const dim3 grid(p.own_tiles, p.splits);
     if (mode == 1) sl_launch<1>(d, grid, s, own, n_own, oth, n_oth, scale, p.per, lse, g, dst, nullptr);
@@ -278,8 +224,8 @@ inline void sl_grad(int mode, const float* own, int n_own, const float* oth, int
 extern "C" int32_t mmrec_score_lse_split_cols(int32_t B, int32_t N, int32_t mode) {
     if (B < 0 || N < 0 || mode < 0 || mode > 2) return 0;
     if ((mode == 2 ? B : N) == 0) return 0;
-    const SlPlan p = mode == 0 ? sl_plan_fwd(B, N) : mode == 1 ? sl_plan_bwd(B, N) : sl_plan_bwd(N, B);
-    return p.per * SL_TILE;
+    const SweepPlan p = mode == 0 ? sl_plan_fwd(B, N) : mode == 1 ? sl_plan_bwd(B, N) : sl_plan_bwd(N, B);
+    return p.per * SWEEP_TILE;
 }
 
 extern "C" size_t mmrec_score_lse_workspace_bytes(int32_t B, int32_t N, int32_t d) {
@@ -300,7 +246,7 @@ extern "C" int mmrec_score_lse_f32(const float* Q, const float* K, int32_t B, in
     float* pm = static_cast<float*>(workspace);
     float* pl = pm;
     if (N > 0) {
-        const SlPlan p = sl_plan_fwd(B, N);
+        const SweepPlan p = sl_plan_fwd(B, N);
         splits = p.splits;
         pl = pm + (size_t)splits * B;
         sl_launch<0>(d, dim3(p.own_tiles, p.splits), s, Q, B, K, N, scale, p.per, nullptr, nullptr, pm, pl);

@@ -14,7 +14,8 @@
 //
 // THE PLAN (what the fuzz's error bound counts).  One 256-thread workgroup per block of R = mmrec_spectrum_rows_per_block(n)
 // consecutive rows, walked as R / 64 tiles of 64 rows.  A tile in LDS is TRANSPOSED, T[slot or column][row] with 68-float rows.
-//   stage   a [64 rows] x [64, 64] product: thread (rg, sg) of 16 x 16 owns rows 4 rg .. + 3 and outputs 4 sg .. + 3; per summed
+//   stage   a [64 rows] x [64, 64] product, tile64.h's t64_stage_nn (F and F^T lie at the tiles' pitch): thread (rg, sg) of
+//           16 x 16 owns rows 4 rg .. + 3 and outputs 4 sg .. + 3; per summed
 //           index one float4 of the tile, one float4 of the matrix and 16 fma onto accumulators that start at 0, the summed
 //           index ascending.  An output therefore meets 64 roundings; the matrix entry's own rounding is counted as 2: S = 66.
 //   filter  lane = row, wave w takes the bins w, w + 4, ...; with (a, b) the image and (c, e) the text spectrum of the bin:
@@ -34,7 +35,7 @@
 //     the blocks l, l + 64, ... in order, then the same butterfly.  NO ATOMICS, every order fixed by n alone.
 // A NULL g_k reads as zeros (its stage is skipped), a NULL output is not computed.  Rows past n are zero in every tile and are
 // never stored.  Workspace: 198 floats per block.  Nothing is allocated, nothing synchronises.
-#include "common.h"
+#include "tile64.h"
 
 namespace {
 
@@ -42,23 +43,17 @@ constexpr int SPC_D = 64;
 constexpr int SPC_BINS = SPC_D / 2 + 1;
 constexpr int SPC_W = 2 * SPC_BINS;              // floats of one filter's weight: [33][2]
 constexpr int SPC_NW = 3 * SPC_W;                // ... and of the three: the partial of a block
-constexpr int SPC_TILE = 64;                     // rows per tile
-constexpr int SPC_LD = 68;                       // floats per tile row: 64 rows + 4, float4 aligned
-constexpr int SPC_TILE_FLOATS = SPC_D * SPC_LD;
-constexpr int SPC_BLOCK = 256;
 constexpr int SPC_MAX_BLOCKS = 1024;             // more rows than 65,536: more tiles per block
 constexpr int SPC_W_LDS = 208;                   // the weights in LDS, padded to a float4 multiple
 constexpr int SPC_FWD_TILES = 4, SPC_BWD_TILES = 6;
 constexpr int SPC_BINS_PER_WAVE = 9;             // wave w of four takes the bins w, w + 4, ...: nine at most
 constexpr int64_t SPC_MAX_ROWS = (int64_t)1 << 30;
 
-constexpr size_t spc_lds_bytes(int tiles) { return sizeof(float) * (2 * SPC_D * SPC_D + SPC_W_LDS + (size_t)tiles * SPC_TILE_FLOATS); }
+// F, F^T and the tiles, all at the T64_LD pitch, and the weights
+constexpr size_t spc_lds_bytes(int tiles) { return sizeof(float) * ((size_t)(2 + tiles) * T64_FLOATS + SPC_W_LDS); }
 
-inline int spc_rows_per_block(int64_t n) {
-    int64_t t = (n + (int64_t)SPC_TILE * SPC_MAX_BLOCKS - 1) / ((int64_t)SPC_TILE * SPC_MAX_BLOCKS);
-    return (int)(t < 1 ? 1 : t) * SPC_TILE;
-}
-inline int spc_blocks(int64_t n) { return n <= 0 ? 0 : (int)((n + spc_rows_per_block(n) - 1) / spc_rows_per_block(n)); }
+inline int spc_rows_per_block(int64_t n) { return t64_rows_per_block(n, SPC_MAX_BLOCKS); }
+inline int spc_blocks(int64_t n) { return t64_blocks(n, SPC_MAX_BLOCKS); }
 
 // cos(2 pi j / 64) rounded from float64; sin(2 pi j / 64) = cos(2 pi (j - 16) / 64)
 __device__ const float SPC_COS[64] = {
@@ -71,97 +66,70 @@ __device__ const float SPC_COS[64] = {
     0.f, 0.0980171412f, 0.195090324f, 0.290284663f, 0.382683426f, 0.471396744f, 0.555570245f, 0.634393275f,
     0.707106769f, 0.773010433f, 0.831469595f, 0.881921291f, 0.923879504f, 0.956940353f, 0.980785251f, 0.99518472f};
 
-struct SpcTile {
-    float4 r[4];      // forward of a stage: r[i] = row 4 rg + i at the outputs 4 sg .. + 3
-};
-
 // F and F^T, and the three weights, into LDS (made visible by the caller's next barrier)
 __device__ __forceinline__ void spc_setup(float* __restrict__ F, float* __restrict__ FT, float* __restrict__ W,
                                           const float* __restrict__ w_img, const float* __restrict__ w_txt,
                                           const float* __restrict__ w_fus) {
-    for (int e = threadIdx.x; e < SPC_D * SPC_D; e += SPC_BLOCK) {
+    for (int e = threadIdx.x; e < SPC_D * SPC_D; e += T64_BLOCK) {
         const int n = e / SPC_D, s = e % SPC_D;
         const int j = (n * (s <= 32 ? s : s - 32)) & 63;
         const float v = s <= 32 ? SPC_COS[j] * 0.125f : -SPC_COS[(j - 16) & 63] * 0.125f;
-        F[e] = v;
-        FT[s * SPC_D + n] = v;
+        F[n * T64_LD + s] = v;
+        FT[s * T64_LD + n] = v;
     }
-    for (int e = threadIdx.x; e < SPC_NW; e += SPC_BLOCK)
+    for (int e = threadIdx.x; e < SPC_NW; e += T64_BLOCK)
         W[e] = e < SPC_W ? w_img[e] : e < 2 * SPC_W ? w_txt[e - SPC_W] : w_fus[e - 2 * SPC_W];
 }
 
-// out[row][o] = sum over s (ascending) of T[s][row] M[s][o], from 0
-__device__ __forceinline__ SpcTile spc_stage(const float* __restrict__ T, const float* __restrict__ M, int rg, int sg) {
-    SpcTile acc;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc.r[i] = f4_zero();
-#pragma unroll 8
-    for (int s = 0; s < SPC_D; ++s) {
-        const float4 t = *reinterpret_cast<const float4*>(T + s * SPC_LD + 4 * rg);
-        const float4 m = *reinterpret_cast<const float4*>(M + s * SPC_D + 4 * sg);
-        acc.r[0] = f4_fma(t.x, m, acc.r[0]);
-        acc.r[1] = f4_fma(t.y, m, acc.r[1]);
-        acc.r[2] = f4_fma(t.z, m, acc.r[2]);
-        acc.r[3] = f4_fma(t.w, m, acc.r[3]);
-    }
-    return acc;
+// the spectrum's stages all start at zero (t64_stage_nn): into a transposed tile, or to a table
+__device__ __forceinline__ void spc_to_tile(float* __restrict__ dst, const float* __restrict__ T, const float* __restrict__ M,
+                                            int rg, int sg) {
+    float4 acc[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
+    t64_stage_nn(T, M, rg, sg, acc);
+    t64_put_t(dst, rg, sg, acc);
+}
+__device__ __forceinline__ void spc_to_table(float* __restrict__ g, long row0, long n, const float* __restrict__ T,
+                                             const float* __restrict__ M, int rg, int sg) {
+    float4 acc[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
+    t64_stage_nn(T, M, rg, sg, acc);
+    t64_store(g, row0, n, rg, sg, acc);
 }
 
-// the thread's 4 x 4 values into a transposed tile: T[4 sg + j][4 rg .. + 3]
-__device__ __forceinline__ void spc_put(float* __restrict__ T, int rg, int sg, const SpcTile& v) {
-    float* __restrict__ p = T + 4 * sg * SPC_LD + 4 * rg;
-    *reinterpret_cast<float4*>(p) = make_float4(v.r[0].x, v.r[1].x, v.r[2].x, v.r[3].x);
-    *reinterpret_cast<float4*>(p + SPC_LD) = make_float4(v.r[0].y, v.r[1].y, v.r[2].y, v.r[3].y);
-    *reinterpret_cast<float4*>(p + 2 * SPC_LD) = make_float4(v.r[0].z, v.r[1].z, v.r[2].z, v.r[3].z);
-    *reinterpret_cast<float4*>(p + 3 * SPC_LD) = make_float4(v.r[0].w, v.r[1].w, v.r[2].w, v.r[3].w);
+// rows row0 .. + 63 of a [n, 64] table into a transposed tile; rows past n are zeros
+__device__ __forceinline__ void spc_rows_to_tile(float* __restrict__ dst, const float* __restrict__ g, long row0, long n, int rg,
+                                                 int sg) {
+    float4 v[4];
+    t64_rows(v, g, row0, n, rg, sg);
+    t64_put_t(dst, rg, sg, v);
 }
 
-// rows row0 + 4 rg .. + 3 of a [n, 64] table at the columns 4 sg .. + 3; rows past n read as zeros
-__device__ __forceinline__ SpcTile spc_load(const float* __restrict__ g, long row0, long n, int rg, int sg) {
-    SpcTile v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long r = row0 + 4 * rg + i;
-        v.r[i] = r < n ? *reinterpret_cast<const float4*>(g + (size_t)r * SPC_D + 4 * sg) : f4_zero();
-    }
-    return v;
-}
-
-__device__ __forceinline__ void spc_store(float* __restrict__ g, long row0, long n, int rg, int sg, const SpcTile& v) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long r = row0 + 4 * rg + i;
-        if (r < n) *reinterpret_cast<float4*>(g + (size_t)r * SPC_D + 4 * sg) = v.r[i];
-    }
-}
-
-__global__ __launch_bounds__(SPC_BLOCK) void spectrum_fwd_kernel(
+__global__ __launch_bounds__(T64_BLOCK) void spectrum_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ w_img, const float* __restrict__ w_txt,
     const float* __restrict__ w_fus, long n, int tiles, float* __restrict__ out_img, float* __restrict__ out_txt,
     float* __restrict__ out_fus) {
     extern __shared__ float4 s_spc[];
     float* F = reinterpret_cast<float*>(s_spc);
-    float* FT = F + SPC_D * SPC_D;
-    float* W = FT + SPC_D * SPC_D;
+    float* FT = F + T64_FLOATS;
+    float* W = FT + T64_FLOATS;
     float* T0 = W + SPC_W_LDS;
-    float* T1 = T0 + SPC_TILE_FLOATS;
-    float* T2 = T1 + SPC_TILE_FLOATS;
-    float* T3 = T2 + SPC_TILE_FLOATS;
+    float* T1 = T0 + T64_FLOATS;
+    float* T2 = T1 + T64_FLOATS;
+    float* T3 = T2 + T64_FLOATS;
     const int rg = threadIdx.x / 16, sg = threadIdx.x % 16;
     const int lane = threadIdx.x % MMREC_WAVE, w = threadIdx.x / MMREC_WAVE;
     spc_setup(F, FT, W, w_img, w_txt, w_fus);
     for (int t = 0; t < tiles; ++t) {
-        const long row0 = ((long)blockIdx.x * tiles + t) * SPC_TILE;
+        const long row0 = ((long)blockIdx.x * tiles + t) * T64;
         if (row0 >= n) break;
-        spc_put(T0, rg, sg, spc_load(x, row0, n, rg, sg));
-        spc_put(T1, rg, sg, spc_load(y, row0, n, rg, sg));
+        spc_rows_to_tile(T0, x, row0, n, rg, sg);
+        spc_rows_to_tile(T1, y, row0, n, rg, sg);
         __syncthreads();
-        spc_put(T2, rg, sg, spc_stage(T0, F, rg, sg));
-        spc_put(T3, rg, sg, spc_stage(T1, F, rg, sg));
+        spc_to_tile(T2, T0, F, rg, sg);
+        spc_to_tile(T3, T1, F, rg, sg);
         __syncthreads();
         for (int k = w; k < SPC_BINS; k += 4) {
             const bool edge = k == 0 || k == SPC_BINS - 1;
-            const int re = k * SPC_LD + lane, im = (32 + k) * SPC_LD + lane;
+            const int re = k * T64_LD + lane, im = (32 + k) * T64_LD + lane;
             const float wk = edge ? 1.f : 2.f;
             const float a = T2[re], c = T3[re];
             const float b = edge ? 0.f : T2[im], e = edge ? 0.f : T3[im];
@@ -179,28 +147,28 @@ __global__ __launch_bounds__(SPC_BLOCK) void spectrum_fwd_kernel(
             }
         }
         __syncthreads();
-        spc_store(out_img, row0, n, rg, sg, spc_stage(T2, FT, rg, sg));
-        spc_store(out_txt, row0, n, rg, sg, spc_stage(T3, FT, rg, sg));
-        spc_store(out_fus, row0, n, rg, sg, spc_stage(T0, FT, rg, sg));
+        spc_to_table(out_img, row0, n, T2, FT, rg, sg);
+        spc_to_table(out_txt, row0, n, T3, FT, rg, sg);
+        spc_to_table(out_fus, row0, n, T0, FT, rg, sg);
         __syncthreads();
     }
 }
 
-__global__ __launch_bounds__(SPC_BLOCK) void spectrum_bwd_kernel(
+__global__ __launch_bounds__(T64_BLOCK) void spectrum_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ w_img, const float* __restrict__ w_txt,
     const float* __restrict__ w_fus, const float* __restrict__ g_img, const float* __restrict__ g_txt,
     const float* __restrict__ g_fus, long n, int tiles, float* __restrict__ dx, float* __restrict__ dy,
     float* __restrict__ part) {
     extern __shared__ float4 s_spc[];
     float* F = reinterpret_cast<float*>(s_spc);
-    float* FT = F + SPC_D * SPC_D;
-    float* W = FT + SPC_D * SPC_D;
+    float* FT = F + T64_FLOATS;
+    float* W = FT + T64_FLOATS;
     float* T0 = W + SPC_W_LDS;               // x, then g_img, then g_fus
-    float* T1 = T0 + SPC_TILE_FLOATS;        // y, then g_txt, then the fusion filter's (dP, dQ)
-    float* T2 = T1 + SPC_TILE_FLOATS;        // (a, b), then (da, db)
-    float* T3 = T2 + SPC_TILE_FLOATS;        // (c, e), then (dc, de)
-    float* T4 = T3 + SPC_TILE_FLOATS;        // the image filter's (dP, dQ)
-    float* T5 = T4 + SPC_TILE_FLOATS;        // the text filter's
+    float* T1 = T0 + T64_FLOATS;             // y, then g_txt, then the fusion filter's (dP, dQ)
+    float* T2 = T1 + T64_FLOATS;             // (a, b), then (da, db)
+    float* T3 = T2 + T64_FLOATS;             // (c, e), then (dc, de)
+    float* T4 = T3 + T64_FLOATS;             // the image filter's (dP, dQ)
+    float* T5 = T4 + T64_FLOATS;             // the text filter's
     const int rg = threadIdx.x / 16, sg = threadIdx.x % 16;
     const int lane = threadIdx.x % MMREC_WAVE, w = threadIdx.x / MMREC_WAVE;
     float wacc[SPC_BINS_PER_WAVE][6];
@@ -210,28 +178,24 @@ __global__ __launch_bounds__(SPC_BLOCK) void spectrum_bwd_kernel(
         for (int j = 0; j < 6; ++j) wacc[i][j] = 0.f;
     spc_setup(F, FT, W, w_img, w_txt, w_fus);
     for (int t = 0; t < tiles; ++t) {
-        const long row0 = ((long)blockIdx.x * tiles + t) * SPC_TILE;
+        const long row0 = ((long)blockIdx.x * tiles + t) * T64;
         if (row0 >= n) break;
-        spc_put(T0, rg, sg, spc_load(x, row0, n, rg, sg));
-        spc_put(T1, rg, sg, spc_load(y, row0, n, rg, sg));
+        spc_rows_to_tile(T0, x, row0, n, rg, sg);
+        spc_rows_to_tile(T1, y, row0, n, rg, sg);
         __syncthreads();
-        {
-            const SpcTile A = spc_stage(T0, F, rg, sg);
-            const SpcTile B = spc_stage(T1, F, rg, sg);
-            spc_put(T2, rg, sg, A);
-            spc_put(T3, rg, sg, B);
-        }
+        spc_to_tile(T2, T0, F, rg, sg);
+        spc_to_tile(T3, T1, F, rg, sg);
         __syncthreads();                                  // every read of the x and y tiles is done
-        if (g_img) spc_put(T0, rg, sg, spc_load(g_img, row0, n, rg, sg));
-        if (g_txt) spc_put(T1, rg, sg, spc_load(g_txt, row0, n, rg, sg));
+        if (g_img) spc_rows_to_tile(T0, g_img, row0, n, rg, sg);
+        if (g_txt) spc_rows_to_tile(T1, g_txt, row0, n, rg, sg);
         __syncthreads();
-        if (g_img) spc_put(T4, rg, sg, spc_stage(T0, F, rg, sg));
-        if (g_txt) spc_put(T5, rg, sg, spc_stage(T1, F, rg, sg));
+        if (g_img) spc_to_tile(T4, T0, F, rg, sg);
+        if (g_txt) spc_to_tile(T5, T1, F, rg, sg);
         __syncthreads();
         if (g_fus) {
-            spc_put(T0, rg, sg, spc_load(g_fus, row0, n, rg, sg));
+            spc_rows_to_tile(T0, g_fus, row0, n, rg, sg);
             __syncthreads();
-            spc_put(T1, rg, sg, spc_stage(T0, F, rg, sg));
+            spc_to_tile(T1, T0, F, rg, sg);
             __syncthreads();
         }
 #pragma unroll
@@ -239,7 +203,7 @@ __global__ __launch_bounds__(SPC_BLOCK) void spectrum_bwd_kernel(
             const int k = w + 4 * i;
             if (k < SPC_BINS) {
                 const bool edge = k == 0 || k == SPC_BINS - 1;
-                const int re = k * SPC_LD + lane, im = (32 + k) * SPC_LD + lane;
+                const int re = k * T64_LD + lane, im = (32 + k) * T64_LD + lane;
                 const float wk = edge ? 1.f : 2.f;
                 const float a = T2[re], c = T3[re];
                 const float b = edge ? 0.f : T2[im], e = edge ? 0.f : T3[im];
@@ -268,8 +232,8 @@ __global__ __launch_bounds__(SPC_BLOCK) void spectrum_bwd_kernel(
             }
         }
         __syncthreads();
-        if (dx) spc_store(dx, row0, n, rg, sg, spc_stage(T2, FT, rg, sg));
-        if (dy) spc_store(dy, row0, n, rg, sg, spc_stage(T3, FT, rg, sg));
+        if (dx) spc_to_table(dx, row0, n, T2, FT, rg, sg);
+        if (dy) spc_to_table(dy, row0, n, T3, FT, rg, sg);
         __syncthreads();
     }
     if (part) {
@@ -290,30 +254,17 @@ __global__ __launch_bounds__(SPC_BLOCK) void spectrum_bwd_kernel(
 }
 
 // every one of the 198 sums a wave: lane l adds the blocks l, l + 64, ... in order, then the butterfly
-__global__ __launch_bounds__(SPC_BLOCK) void spectrum_finish_kernel(const float* __restrict__ part, int nb,
+__global__ __launch_bounds__(T64_BLOCK) void spectrum_finish_kernel(const float* __restrict__ part, int nb,
                                                                     float* __restrict__ dw_img, float* __restrict__ dw_txt,
                                                                     float* __restrict__ dw_fus) {
     const int lane = threadIdx.x % MMREC_WAVE;
-    const int o = blockIdx.x * (SPC_BLOCK / MMREC_WAVE) + threadIdx.x / MMREC_WAVE;
+    const int o = blockIdx.x * (T64_BLOCK / MMREC_WAVE) + threadIdx.x / MMREC_WAVE;
     if (o >= SPC_NW) return;
     float a = 0.f;
     for (int b = lane; b < nb; b += MMREC_WAVE) a += part[(size_t)b * SPC_NW + o];
     a = wave_sum(a);
     float* __restrict__ dw = o < SPC_W ? dw_img : o < 2 * SPC_W ? dw_txt : dw_fus;
     if (lane == 0 && dw) dw[o % SPC_W] = a;
-}
-
-// more LDS than a kernel gets by default: asked for once per device, outside any launch
-int spc_allow_lds(const void* kernel, size_t bytes, bool* done) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return (int)e;
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-    return 0;
 }
 
 }  // namespace
@@ -333,10 +284,10 @@ extern "C" int mmrec_spectrum_fwd_f32(const float* x, const float* y, const floa
     if (n == 0) return 0;
     if (!x || !y || !w_img || !w_txt || !w_fus || !out_img || !out_txt || !out_fus) return MMREC_ERR_BAD_ARG;
     static bool lds_ok[64];
-    const int rc = spc_allow_lds(reinterpret_cast<const void*>(spectrum_fwd_kernel), spc_lds_bytes(SPC_FWD_TILES), lds_ok);
+    const int rc = t64_allow_lds(reinterpret_cast<const void*>(spectrum_fwd_kernel), spc_lds_bytes(SPC_FWD_TILES), lds_ok);
     if (rc) return rc;
-    hipLaunchKernelGGL(spectrum_fwd_kernel, dim3(spc_blocks(n)), dim3(SPC_BLOCK), spc_lds_bytes(SPC_FWD_TILES),
-                       mmrec_stream(stream), x, y, w_img, w_txt, w_fus, (long)n, spc_rows_per_block(n) / SPC_TILE, out_img, out_txt,
+    hipLaunchKernelGGL(spectrum_fwd_kernel, dim3(spc_blocks(n)), dim3(T64_BLOCK), spc_lds_bytes(SPC_FWD_TILES),
+                       mmrec_stream(stream), x, y, w_img, w_txt, w_fus, (long)n, spc_rows_per_block(n) / T64, out_img, out_txt,
                        out_fus);
     MMREC_RETURN_LAUNCH_STATUS();
 }
@@ -352,15 +303,15 @@ extern "C" int mmrec_spectrum_bwd_f32(const float* x, const float* y, const floa
     if (!x || !y || !w_img || !w_txt || !w_fus || (want_w && !workspace)) return MMREC_ERR_BAD_ARG;
     if (!want_w && !dx && !dy) return 0;
     static bool lds_ok[64];
-    const int rc = spc_allow_lds(reinterpret_cast<const void*>(spectrum_bwd_kernel), spc_lds_bytes(SPC_BWD_TILES), lds_ok);
+    const int rc = t64_allow_lds(reinterpret_cast<const void*>(spectrum_bwd_kernel), spc_lds_bytes(SPC_BWD_TILES), lds_ok);
     if (rc) return rc;
     hipStream_t s = mmrec_stream(stream);
     float* part = want_w ? static_cast<float*>(workspace) : nullptr;
     const int nb = spc_blocks(n);
-    hipLaunchKernelGGL(spectrum_bwd_kernel, dim3(nb), dim3(SPC_BLOCK), spc_lds_bytes(SPC_BWD_TILES), s, x, y, w_img, w_txt, w_fus,
-                       g_img, g_txt, g_fus, (long)n, spc_rows_per_block(n) / SPC_TILE, dx, dy, part);
+    hipLaunchKernelGGL(spectrum_bwd_kernel, dim3(nb), dim3(T64_BLOCK), spc_lds_bytes(SPC_BWD_TILES), s, x, y, w_img, w_txt, w_fus,
+                       g_img, g_txt, g_fus, (long)n, spc_rows_per_block(n) / T64, dx, dy, part);
     if (want_w)
-        hipLaunchKernelGGL(spectrum_finish_kernel, dim3((SPC_NW + SPC_BLOCK / MMREC_WAVE - 1) / (SPC_BLOCK / MMREC_WAVE)),
-                           dim3(SPC_BLOCK), 0, s, part, nb, dw_img, dw_txt, dw_fus);
+        hipLaunchKernelGGL(spectrum_finish_kernel, dim3((SPC_NW + T64_BLOCK / MMREC_WAVE - 1) / (T64_BLOCK / MMREC_WAVE)),
+                           dim3(T64_BLOCK), 0, s, part, nb, dw_img, dw_txt, dw_fus);
     MMREC_RETURN_LAUNCH_STATUS();
 }

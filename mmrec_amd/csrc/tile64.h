@@ -1,5 +1,5 @@
 // [64 rows] x [64, 64] products on a 256-thread workgroup, fp32 VALU fma, both operands in LDS: the stage of the row-wise fusers
-// (modal_fusion.hip; written to be shared with the next one of the family).
+// (modal_fusion.hip: row-major tiles, both forms; spectrum.hip: transposed tiles filled from registers, t64_stage_nn only).
 //
 // Every tile and every matrix is 64 x 64 floats with rows of T64_LD = 68 floats (float4 aligned, and 17 sixteen-byte slots: the
 // 16 lanes of a read that walk 16 rows hit 16 different slots).  Thread (rg, sg) = (tid / 16, tid % 16) always owns the tile
@@ -16,6 +16,15 @@ constexpr int T64_LD = 68;
 constexpr int T64_FLOATS = T64 * T64_LD;
 constexpr int T64_BLOCK = 256;
 
+// the plan of a fuser: 64 rows per workgroup while max_blocks workgroups cover the n rows, then more tiles per workgroup
+static inline int t64_rows_per_block(int64_t n, int max_blocks) {
+    const int64_t t = (n + (int64_t)T64 * max_blocks - 1) / ((int64_t)T64 * max_blocks);
+    return (int)(t < 1 ? 1 : t) * T64;
+}
+static inline int t64_blocks(int64_t n, int max_blocks) {
+    return n <= 0 ? 0 : (int)((n + t64_rows_per_block(n, max_blocks) - 1) / t64_rows_per_block(n, max_blocks));
+}
+
 // a row-major [64][64] matrix of global memory into an LDS image with T64_LD rows (visible after the caller's next barrier)
 __device__ __forceinline__ void t64_matrix(float* __restrict__ L, const float* __restrict__ g) {
     for (int e = threadIdx.x; e < T64 * T64 / 4; e += T64_BLOCK) {
@@ -31,6 +40,15 @@ __device__ __forceinline__ void t64_load(float* __restrict__ R, const float* __r
         const long r = row0 + 4 * rg + i;
         *reinterpret_cast<float4*>(R + (4 * rg + i) * T64_LD + 4 * sg) =
             (g && r < n) ? *reinterpret_cast<const float4*>(g + (size_t)r * T64 + 4 * sg) : f4_zero();
+    }
+}
+
+// rows row0 + 4 rg + i of a [n, 64] table at the columns 4 sg .. + 3 into registers (layout L0); rows past n read as zeros
+__device__ __forceinline__ void t64_rows(float4 (&v)[4], const float* __restrict__ g, long row0, long n, int rg, int sg) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long r = row0 + 4 * rg + i;
+        v[i] = r < n ? *reinterpret_cast<const float4*>(g + (size_t)r * T64 + 4 * sg) : f4_zero();
     }
 }
 
@@ -92,6 +110,15 @@ __device__ __forceinline__ void t64_put(float* __restrict__ R, float* __restrict
         for (int i = 0; i < 4; ++i) R[(4 * rg + i) * T64_LD + c] = v[i][j];
         if (Tt) *reinterpret_cast<float4*>(Tt + c * T64_LD + 4 * rg) = make_float4(v[0][j], v[1][j], v[2][j], v[3][j]);
     }
+}
+
+// layout L0 values into a TRANSPOSED tile: Tt[4 sg + j][4 rg .. + 3]
+__device__ __forceinline__ void t64_put_t(float* __restrict__ Tt, int rg, int sg, const float4 (&v)[4]) {
+    float* __restrict__ p = Tt + 4 * sg * T64_LD + 4 * rg;
+    *reinterpret_cast<float4*>(p) = make_float4(v[0].x, v[1].x, v[2].x, v[3].x);
+    *reinterpret_cast<float4*>(p + T64_LD) = make_float4(v[0].y, v[1].y, v[2].y, v[3].y);
+    *reinterpret_cast<float4*>(p + 2 * T64_LD) = make_float4(v[0].z, v[1].z, v[2].z, v[3].z);
+    *reinterpret_cast<float4*>(p + 3 * T64_LD) = make_float4(v[0].w, v[1].w, v[2].w, v[3].w);
 }
 
 // more LDS than a kernel gets by default: asked for once per device, outside any launch

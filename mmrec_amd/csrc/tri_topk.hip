@@ -4,10 +4,10 @@
 //   list t of row r = the k columns with the largest S_t[r, .], score descending, ties by the lower column (cand_before).
 // A list needs all three modalities' scores of a (row, column) pair at once, so no two-operand top-k serves it.
 //
-// One sweep in the manner of score_lse.hip MODE 0 and the FUSED form of topk.hip.  A workgroup (4 waves) owns 128 query rows,
-// a wave 32 of them: the three gathered query fragments stay in registers (lane (i, h) holds T_m[ids[q0 + i]][2 s + h], 3 x 32
-// VGPRs).  64-row tiles of the three tables reach the waves through LDS, fetched one tile ahead and stored de-interleaved as in
-// score_lse.hip.  Per 32-row sub-tile three v_mfma_f32_32x32x2_f32 chains in the swapped orientation: a lane holds ONE query
+// One sweep of mfma_sweep.h (as score_lse.hip MODE 0) and the FUSED form of topk.hip.  A workgroup (4 waves) owns 128 query
+// rows, a wave 32 of them: the three gathered query fragments stay in registers (lane (i, h) holds T_m[ids[q0 + i]][2 s + h],
+// 3 x 32 VGPRs).  64-row tiles of the three tables reach the waves through LDS, fetched one tile ahead and stored de-interleaved
+// (mfma_sweep.h).  Per 32-row sub-tile three v_mfma_f32_32x32x2_f32 chains in the swapped orientation: a lane holds ONE query
 // and 16 candidates, so a list's running threshold is one register.  Per candidate three exp and three mixes; the common
 // path of a list is 16 compares.
 // Survivors go to lists in LDS, PRIVATE to a lane (one query x one half of the candidate rows) and to one of the three targets:
@@ -20,38 +20,19 @@
 // Columns are split over gridDim.y by a plan of (B, N) alone; every split hands its sorted, cut lists to `tt_finish_kernel`,
 // which ranks the <= 32 k entries of a (target, row) by counting.  No atomics; a call always gives the same bits; no
 // allocation, no synchronisation: capturable.
-#include "mfma_stream.h"
+#include "mfma_sweep.h"
 #include "topk_sort.h"
 
 namespace {
 
-constexpr int TT_OWN = 128;          // query rows per workgroup
-constexpr int TT_TILE = 64;          // table rows per LDS tile
-constexpr int TT_LD = 68;            // tile pitch (score_lse.hip)
+constexpr int TT_LD = 64 + 4;        // tile pitch (mfma_sweep.h)
 constexpr int TT_CAP = 16;           // list slots per (lane, target); slot TT_CAP is the dump
 constexpr int TT_KMAX = 16;
 constexpr int TT_WGS = 512;          // workgroups the grid aims at
 constexpr int TT_SPLITS_MAX = 32;    // 32 * 16 = 512 merge slots
 constexpr int TT_ROWS_MAX = 1 << 30;
 
-struct TtPlan {
-    int own_tiles, col_tiles, per, splits;
-};
-// a function of the two sizes only
-inline TtPlan tt_plan(long B, long N) {
-    TtPlan p;
-    p.own_tiles = (int)((B + TT_OWN - 1) / TT_OWN);
-    p.col_tiles = (int)((N + TT_TILE - 1) / TT_TILE);
-    const long own = p.own_tiles > 0 ? p.own_tiles : 1;
-    long want = (TT_WGS + own - 1) / own;
-    if (want > TT_SPLITS_MAX) want = TT_SPLITS_MAX;
-    if (want > p.col_tiles) want = p.col_tiles;
-    if (want < 1) want = 1;
-    p.per = (int)((p.col_tiles + want - 1) / want);
-    if (p.per < 1) p.per = 1;
-    p.splits = p.col_tiles > 0 ? (p.col_tiles + p.per - 1) / p.per : 1;
-    return p;
-}
+inline SweepPlan tt_plan(long B, long N) { return sweep_plan(B, N, TT_WGS, TT_SPLITS_MAX); }
 
 __device__ __forceinline__ float tt_max8(const float* a) {
     return fmaxf(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])), fmaxf(fmaxf(a[4], a[5]), fmaxf(a[6], a[7])));
@@ -62,13 +43,13 @@ __global__ __launch_bounds__(256) void tt_sweep_kernel(const float* __restrict__
                                                        const int64_t* __restrict__ ids, int B,
                                                        const float* __restrict__ lse, const float* __restrict__ W, int k,
                                                        int per, int* __restrict__ tmp_idx, float* __restrict__ tmp_val) {
-    __shared__ __attribute__((aligned(16))) float T[3][TT_TILE * TT_LD];
+    __shared__ __attribute__((aligned(16))) float T[3][SWEEP_TILE * TT_LD];
     __shared__ unsigned long long L[256 * 3][TT_CAP + 1];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, h = lane >> 5;
-    const int q0 = blockIdx.x * TT_OWN + wave * 32;
-    const int col_tiles = (N + TT_TILE - 1) / TT_TILE;
+    const int q0 = blockIdx.x * SWEEP_OWN + wave * 32;
+    const int col_tiles = (N + SWEEP_TILE - 1) / SWEEP_TILE;
     const int t_begin = blockIdx.y * per, t_end = min(t_begin + per, col_tiles);
     const float* const tabs[3] = {T0, T1, T2};
     unsigned long long (*Lw)[TT_CAP + 1] = L + wave * 64 * 3;     // this wave's lists: [(lane_in_wave * 3 + target)][slot]
@@ -82,9 +63,7 @@ __global__ __launch_bounds__(256) void tt_sweep_kernel(const float* __restrict__
     float own_l[3];
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
-        const float* src = tabs[m] + (size_t)(q_ok ? id : 0) * 64 + h;
-#pragma unroll
-        for (int s = 0; s < 32; ++s) qf[m][s] = q_ok ? src[2 * s] : 0.f;
+        sweep_own<64>(qf[m], tabs[m] + (size_t)(q_ok ? id : 0) * 64, q_ok, h);
         own_l[m] = q_ok ? lse[(size_t)m * B + row] : 0.f;
     }
     float w[3][3];
@@ -95,25 +74,12 @@ __global__ __launch_bounds__(256) void tt_sweep_kernel(const float* __restrict__
 
     float4 pre[3][4];
     auto fetch = [&](int t) {
-        const int o0 = t * TT_TILE;
 #pragma unroll
-        for (int m = 0; m < 3; ++m)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int e = tid + 256 * j, r = e >> 4, c4 = e & 15;
-                pre[m][j] = ld4_guard(tabs[m] + (size_t)(o0 + r < N ? o0 + r : 0) * 64 + 4 * c4, o0 + r < N);
-            }
+        for (int m = 0; m < 3; ++m) sweep_fetch<64>(pre[m], tabs[m], t * SWEEP_TILE, N, tid);
     };
     auto stage = [&]() {
 #pragma unroll
-        for (int m = 0; m < 3; ++m)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int e = tid + 256 * j, r = e >> 4, c4 = e & 15;
-                float* dst = T[m] + r * TT_LD;
-                *reinterpret_cast<float2*>(dst + 2 * c4) = make_float2(pre[m][j].x, pre[m][j].z);
-                *reinterpret_cast<float2*>(dst + 32 + 2 * c4) = make_float2(pre[m][j].y, pre[m][j].w);
-            }
+        for (int m = 0; m < 3; ++m) sweep_stage<64>(T[m], pre[m], tid);
     };
 
     // keep a score iff s > teff: -inf until the list's first cut, the strict k-th score after it
@@ -123,11 +89,6 @@ __global__ __launch_bounds__(256) void tt_sweep_kernel(const float* __restrict__
     // sort target t's entries of query qq (both half lists, n0 + n1 <= 64), keep the best min(n, k) split back over the halves;
     // returns the k-th score or -inf when fewer than k entries exist.  The lists are private to the wave and a wave's LDS
     // operations complete in order: only the compiler must keep the order.
-    auto wave_sync = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     auto gather = [&](int t, int qq, int n0, int n1) -> Cand {
         Cand x{-INFINITY, INT_MAX};
         if (lane < n0) x = unpack_cand(Lw[qq * 3 + t][lane]);
@@ -137,14 +98,14 @@ __global__ __launch_bounds__(256) void tt_sweep_kernel(const float* __restrict__
     auto compact = [&](int t, int qq, int& my_cnt) -> float {
         const int n0 = __shfl(my_cnt, qq, 64), n1 = __shfl(my_cnt, qq + 32, 64);
         const int n = n0 + n1;
-        wave_sync();
+        wave_lds_order();
         Cand x = gather(t, qq, n0, n1);
         bitonic64(x, lane);
         const int keep = min(n, k), h0 = (keep + 1) >> 1;
-        wave_sync();
+        wave_lds_order();
         if (lane < h0) Lw[qq * 3 + t][lane] = pack_cand(x.v, x.i);
         else if (lane < keep) Lw[(qq + 32) * 3 + t][lane - h0] = pack_cand(x.v, x.i);
-        wave_sync();
+        wave_lds_order();
         if (lane == qq) my_cnt = h0;
         if (lane == qq + 32) my_cnt = keep - h0;
         return n >= k ? __shfl(x.v, k - 1, 64) : -INFINITY;
@@ -156,24 +117,13 @@ __global__ __launch_bounds__(256) void tt_sweep_kernel(const float* __restrict__
         stage();
         __syncthreads();
         if (tl + 1 < t_end) fetch(tl + 1);         // in flight under this tile's MFMAs
-        const int o0 = tl * TT_TILE;
+        const int o0 = tl * SWEEP_TILE;
 #pragma unroll 1
         for (int u = 0; u < 2; ++u) {
             if (o0 + 32 * u >= N) break;           // uniform: nothing but padding in this sub-tile
             f32x16 acc[3];
 #pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                acc[m] = f32x16{0};
-                const float* tr = T[m] + (32 * u + i) * TT_LD + h * 32;
-#pragma unroll
-                for (int q4 = 0; q4 < 8; ++q4) {
-                    const float4 a = *reinterpret_cast<const float4*>(tr + 4 * q4);
-                    acc[m] = mfma32(a.x, qf[m][4 * q4 + 0], acc[m]);
-                    acc[m] = mfma32(a.y, qf[m][4 * q4 + 1], acc[m]);
-                    acc[m] = mfma32(a.z, qf[m][4 * q4 + 2], acc[m]);
-                    acc[m] = mfma32(a.w, qf[m][4 * q4 + 3], acc[m]);
-                }
-            }
+            for (int m = 0; m < 3; ++m) acc[m] = sweep_scores<64>(T[m], u, i, h, qf[m]);
             float p[3][16];
 #pragma unroll
             for (int m = 0; m < 3; ++m)
@@ -230,7 +180,7 @@ __global__ __launch_bounds__(256) void tt_sweep_kernel(const float* __restrict__
         for (int qq = 0; qq < 32; ++qq) {
             if (q0 + qq >= B) break;               // uniform
             const int n0 = __shfl(my_cnt, qq, 64), n1 = __shfl(my_cnt, qq + 32, 64);
-            wave_sync();
+            wave_lds_order();
             Cand x = gather(t, qq, n0, n1);
             bitonic64(x, lane);
             if (lane < k) {
@@ -309,7 +259,7 @@ __global__ __launch_bounds__(256) void list_exclude_kernel(const int32_t* __rest
 
 extern "C" int32_t mmrec_tri_topk_split_cols(int32_t B, int32_t N) {
     if (B < 0 || N <= 0 || B > TT_ROWS_MAX || N > TT_ROWS_MAX) return 0;
-    return tt_plan(B, N).per * TT_TILE;      // <= 2^30 + 63
+    return tt_plan(B, N).per * SWEEP_TILE;      // <= 2^30 + 63
 }
 
 extern "C" size_t mmrec_tri_topk_workspace_bytes(int32_t B, int32_t N, int32_t k) {
@@ -325,7 +275,7 @@ extern "C" int mmrec_tri_topk_f32(const float* T0, const float* T1, const float*
     if (B > TT_ROWS_MAX || N > TT_ROWS_MAX) return MMREC_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     if (!W || !out_idx || !ws) return MMREC_ERR_BAD_ARG;
-    const TtPlan p = tt_plan(B, N);
+    const SweepPlan p = tt_plan(B, N);
     hipStream_t s = mmrec_stream(stream);
     int* tmp_idx = static_cast<int*>(ws);
     float* tmp_val = reinterpret_cast<float*>(tmp_idx + (size_t)p.splits * 3 * (size_t)B * k);

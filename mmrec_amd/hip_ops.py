@@ -112,6 +112,13 @@ def _chk(t, dtype, name, dim=None):
     return t
 
 
+def _dev_table(t, width=None, max_rows=None):
+    """the operand test of the `*_served` predicates: a device fp32 contiguous 2-D tensor, of `width` columns and at most
+    `max_rows` rows where given"""
+    return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+                and (width is None or t.shape[1] == width) and (max_rows is None or t.shape[0] <= max_rows))
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
@@ -1577,8 +1584,7 @@ def linear(X, W, b=None):
 def linear_rows_served(table, ids, W):
     """True where `linear_rows` runs the gathered kernels (mmrec_linear_rows_*): device fp32 operands, W [64, F] with
     F % 128 == 0, a contiguous table, int64 ids, and the split-operand projection (`LINEAR_F16X3`) on."""
-    return (LINEAR_F16X3 and isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and
-            table.dim() == 2 and table.is_contiguous() and W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and
+    return (LINEAR_F16X3 and _dev_table(table) and W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and
             W.shape[0] == 64 and W.shape[1] == table.shape[1] and table.shape[1] % 128 == 0 and
             isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 1)
 
@@ -2136,13 +2142,9 @@ def _edge_width_served(d):
 def edge_dot_served(A, B, rows, cols):
     """True where `edge_dot` runs the kernels (mmrec_edge_dot_*): device fp32 contiguous 2-D A, B of one served width (8 /
     16 / 32 or 64 k <= 384: spmm_raw's), int64 1-D device rows / cols of equal length, and the `EDGE_DOT` switch on."""
-    def table(t):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
-                t.is_contiguous())
-
     def ids(t):
         return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
-    return bool(EDGE_DOT and table(A) and table(B) and A.shape[1] == B.shape[1] and _edge_width_served(A.shape[1]) and
+    return bool(EDGE_DOT and _dev_table(A) and _dev_table(B) and A.shape[1] == B.shape[1] and _edge_width_served(A.shape[1]) and
                 ids(rows) and ids(cols) and rows.numel() == cols.numel())
 
 
@@ -2328,8 +2330,7 @@ def edge_attention_served(Q, KV, dyn):
     """True where `edge_attention` runs the kernel: device fp32 contiguous [*, 64] tables with one row of Q per row of `dyn`
     and one row of KV per column, and the `EDGE_ATTENTION` switch on.  `Q is KV` is allowed."""
     def table(t, n):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
-                t.shape[1] == EMB_DIM and t.is_contiguous() and t.shape[0] == n)
+        return _dev_table(t, EMB_DIM) and t.shape[0] == n
     return bool(EDGE_ATTENTION and table(Q, dyn.n_rows) and table(KV, dyn.n_cols))
 
 
@@ -2478,8 +2479,7 @@ def neighbor_max_torch(X, rows, cols, n_rows):
 def neighbor_max_served(X, dyn):
     """True where `neighbor_max` runs the kernels: a device fp32 contiguous [dyn.n_cols, 64] table over a `DynGraph` that
     holds both CSR forms, and the `NEIGHBOR_MAX` switch on."""
-    return bool(NEIGHBOR_MAX and isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and
-                X.shape[1] == EMB_DIM and X.is_contiguous() and X.shape[0] == dyn.n_cols and hasattr(dyn, "side"))
+    return bool(NEIGHBOR_MAX and _dev_table(X, EMB_DIM) and X.shape[0] == dyn.n_cols and hasattr(dyn, "side"))
 
 
 class _NeighborMax(torch.autograd.Function):
@@ -2547,8 +2547,7 @@ def score_lse_split_cols(B, N, mode=0):
 def score_lse_served(Q, K):
     """True where `score_lse` runs the kernel: device fp32 contiguous [B, d] and [N, d] with d 64 or 128.  `Q is K` is allowed."""
     def table(t):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
-                t.shape[1] in SCORE_LSE_WIDTHS and t.is_contiguous() and t.shape[0] <= (1 << 30))
+        return _dev_table(t, max_rows=1 << 30) and t.shape[1] in SCORE_LSE_WIDTHS
     return bool(table(Q) and table(K) and Q.shape[1] == K.shape[1])
 
 
@@ -2623,16 +2622,11 @@ def tri_topk_split_cols(B, N):
     return int(_lib.load().mmrec_tri_topk_split_cols(int(B), int(N)))
 
 
-def _tri_dev(t, dtype, shape):
-    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and
-            tuple(t.shape) == tuple(shape))
-
-
 def _tri_tables_served(tables, k):
     if not (isinstance(tables, (tuple, list)) and len(tables) == 3 and isinstance(tables[0], torch.Tensor) and tables[0].dim() == 2):
         return False
     N = tables[0].shape[0]
-    return bool(all(_tri_dev(t, torch.float32, (N, EMB_DIM)) for t in tables) and 1 <= k <= TRI_TOPK_KMAX and k <= N <= (1 << 30))
+    return bool(all(_dev_table(t, EMB_DIM) and t.shape[0] == N for t in tables) and 1 <= k <= TRI_TOPK_KMAX and k <= N <= (1 << 30))
 
 
 def tri_softmax_topk_served(tables, ids, lse, W, k):
@@ -2641,8 +2635,9 @@ def tri_softmax_topk_served(tables, ids, lse, W, k):
     if not (TRI_TOPK and _tri_tables_served(tables, k) and isinstance(lse, torch.Tensor) and lse.dim() == 2):
         return False
     B = lse.shape[1]
-    return bool(B <= (1 << 30) and (ids is None or _tri_dev(ids, torch.int64, (B,))) and
-                _tri_dev(lse, torch.float32, (3, B)) and _tri_dev(W, torch.float32, (3, 3)))
+    dev_ids = ids is None or (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int64 and
+                              ids.is_contiguous() and tuple(ids.shape) == (B,))
+    return bool(B <= (1 << 30) and dev_ids and _dev_table(lse, B) and lse.shape[0] == 3 and _dev_table(W, 3) and W.shape[0] == 3)
 
 
 def tri_softmax_topk_torch(tables, ids, lse, W, k, return_values=False):
@@ -2770,8 +2765,7 @@ def hyper_rows_per_block(n):
 
 
 def _hyper_table(t, width=None):
-    return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
-                and t.shape[0] <= (1 << 30) and (t.shape[1] == width if width else 1 <= t.shape[1] <= HYPER_H_MAX))
+    return _dev_table(t, width, 1 << 30) and (width is not None or 1 <= t.shape[1] <= HYPER_H_MAX)
 
 
 def hyper_assign_torch(logits, noise, keep_mask=None, tau=1.0, keep_rate=1.0):
@@ -2958,8 +2952,7 @@ def spectrum_fusion_served(image, text, w_img, w_txt, w_fus):
     """True where `spectrum_fusion` runs the kernels: device fp32 contiguous [I, 64] tables of one shape, 1 <= I <= 2^30,
     device fp32 contiguous [1, 33, 2] weights, the `SPECTRUM` switch on."""
     def table(t):
-        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
-                    t.is_contiguous() and t.shape[1] == EMB_DIM and 1 <= t.shape[0] <= (1 << 30))
+        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
 
     def weight(t):
         return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
@@ -3049,7 +3042,7 @@ def modal_fusion_served(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
                     (shape is None or tuple(t.shape) == shape))
 
     def table(t):
-        return ok(t) and t.dim() == 2 and t.shape[1] == EMB_DIM and 1 <= t.shape[0] <= (1 << 30)
+        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
     if not (MODAL_FUSION and table(V) and table(T) and table(C) and V.shape == T.shape == C.shape):
         return False
     return bool(all(ok(w, (EMB_DIM, EMB_DIM)) for w in (Wq, Wv, Wt)) and all(ok(b, (EMB_DIM,)) for b in (bq, bv, bt)) and

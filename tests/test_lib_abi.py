@@ -130,3 +130,27 @@ def test_topk_workspace_covers_both_kd64_paths(lib):
     big = lib.mmrec_topk_workspace_bytes(20000, 500000, 64, 50)
     assert 0 < big <= 9 * 2 ** 30            # one 8 GB score block of the materialised path at most
     assert lib.mmrec_topk_workspace_bytes(0, 10, 64, 5) == 0
+
+
+def test_tile_and_sweep_plans(lib):
+    """The plan exports of the ops on tile64.h and mfma_sweep.h, which launch nothing.  The literals follow from the plans'
+    definitions: a fuser's workgroup takes 64 rows while `cap` workgroups cover the table (spectrum 1024, modal fusion 256), then
+    ceil(n / (64 cap)) tiles of 64; a sweep has ceil(own / 128) own tiles, asks for ceil(target / own tiles) splits, at most its
+    cap and at most the ceil(other / 64) tiles there are, and gives a split ceil(tiles / splits) tiles of 64 rows."""
+    rows = lib.mmrec_spectrum_rows_per_block
+    assert [rows(n) for n in (0, 1, 65536)] == [64, 64, 64]       # 1024 blocks of 64 rows
+    assert rows(65537) == 128
+    assert rows(2 ** 30) == 1048576                                # 2^30 / 65,536 = 16,384 tiles of 64
+    assert rows(2 ** 30 + 1) == 0 and rows(-1) == 0
+    rows = lib.mmrec_modal_fusion_rows_per_block
+    assert rows(16384) == 64 and rows(16385) == 128                # 256 blocks of 64 rows
+    assert rows(2 ** 30) == 4194304                                # 2^30 / 16,384 = 65,536 tiles of 64
+    # 65,537 rows in blocks of 128: 513 blocks of 198 floats; 16,385 rows in blocks of 128: 129 blocks of 12,544 floats
+    assert lib.mmrec_spectrum_workspace_bytes(65537) == 513 * 198 * 4 == 406296
+    assert lib.mmrec_modal_fusion_workspace_bytes(16385) == 129 * 12544 * 4 == 6472704
+    # one own tile, 1000 tiles of the table: the forward LSE may split 64 ways (16 tiles each), the tri-top-k 32 ways (32 each)
+    assert lib.mmrec_score_lse_split_cols(128, 64000, 0) == 1024
+    assert lib.mmrec_tri_topk_split_cols(128, 64000) == 2048
+    # 16 own tiles, target 512: 32 splits of the 111 tiles, 4 tiles each -- the same plan in both ops
+    assert lib.mmrec_score_lse_split_cols(2048, 7050, 0) == 256
+    assert lib.mmrec_tri_topk_split_cols(2048, 7050) == 256

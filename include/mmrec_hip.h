@@ -740,6 +740,71 @@ int mmrec_modal_fusion_bwd_f32(const float* V, const float* T, const float* C, c
                                float* dq, float* dWv, float* dbv, float* dWt, float* dbt, void* workspace,
                                mmrec_stream_t stream);
 
+/* MVGAE's posterior tail over [n, 64] tables: two products of experts, four reparametrisations, four KL terms and the
+ * evaluation table, with its backward.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: product_of_experts twice, reparametrize four times, kl_loss four times and sigmoid(pd_mu) -- mvgae.py, forward and
+ *           calculate_loss -- and autograd's mirror of them: about 140 element-wise launches forward.
+ *
+ * mu_v, lv_v, mu_t, lv_t, mu_c, lv_c [n, 64]: the image, text and collaborative encoders' means and log-variances.  E_p, E_v,
+ * E_t, E_c [n, 64]: the noise of the four reparametrisations, ALL given or ALL NULL (NULL: Z[k] = mu_k, evaluation mode).
+ * eps = 1e-8f; it, 0.1f and 0.05f below are the fp32 constants.  Per element,
+ *   PoE((mu_a, l_a), (mu_b, l_b)):  T_x = 1 / (exp(l_x) + eps),  S = T_a + T_b,  var = 1 / S,  m = (mu_a T_a + mu_b T_b) var,
+ *                                   l = log(var)
+ *   (m1, l1) = PoE(v, t);   (mu_p, l_p) = PoE((m1, l1), c)        l1 enters stage 2 as it is: NOT clamped, as in the reference
+ *   for k in (p, v, t, c):  lh_k = min(l_k, 10),  Z[k] = mu_k + 0.1 E_k exp(0.5 lh_k)            Z [4, n, 64], order p, v, t, c
+ *                           kl[k] = -0.5 / n  sum over rows and columns of (1 + lh_k - mu_k^2 - exp(lh_k))          kl [4]
+ *   score = sigmoid(mu_p)                                                                          [n, 64]
+ * SUPPORTED DOMAIN: finite inputs with |lv| <= 30.  Over it every intermediate is a normal fp32 number (exp(l) in 9e-14 .. 1.1e13,
+ * T in 9e-14 .. 1e8, T^2 <= 1e16, S in 1.8e-13 .. 2e8) and every output and gradient is finite.  Outside it the kernels do not
+ * fault (no address depends on the data), and nothing more is promised.
+ *
+ * THE PLAN.  A 16-lane group per row, one float4 per lane and table.  One 256-thread workgroup per block of
+ * R = mmrec_posterior_fusion_rows_per_block(n) = 16 ceil(n / 16,384) consecutive rows (a multiple of 16, a function of n alone, at
+ * most 1,024 blocks), walked in R / 16 passes of 16 rows: group g of pass p has the row  block R + 16 p + g.  All arithmetic is
+ * fp32; every operation named below is ONE rounding (an fma is one), in this order (where a product feeds only an addition the
+ * compiler may contract the two into one fma: a rounding fewer, never one more):
+ *   expert   E = expf(l), T = 1 / (E + eps)                          (stage 2's first expert: E = expf(l1), l1 the logf below)
+ *   PoE      S = T_a + T_b, var = 1 / S, m = fma(mu_b, T_b, mu_a T_a) var, l = logf(var)
+ *   tail     lh = fminf(l, 10), sd = expf(0.5 lh), el = expf(lh), Z = fma(0.1 E_k, sd, mu);  noise NULL: Z = mu, a copy of the bits
+ *   KL term  t = fma(-mu, mu, 1 + lh) - el.  A lane adds its four columns in order, ((t_0 + t_1) + t_2) + t_3: 3 additions; the 16
+ *            lanes of the row by a butterfly (xor 8, 4, 2, 1): 4; the group adds its rows pass after pass onto one sum from 0:
+ *            R / 16; the 16 groups are added in order from 0: 16.  One partial per block and k: the workspace is [blocks][4].
+ *   finish   a second launch of ONE workgroup, wave k for kl[k]: lane j adds the blocks j, j + 64, ... in order from 0
+ *            (ceil(blocks / 64) additions), the 64 lanes by a butterfly (xor 32, 16, 8, 4, 2, 1): 6;
+ *            kl[k] = (-0.5 inv_n) sum, inv_n = 1 / (float)n rounded once on the host.
+ *            In all a term meets 3 + 4 + R / 16 + 16 + ceil(blocks / 64) + 6 additions.
+ *   sigmoid  q = expf(-|z|), score = (z >= 0 ? 1 : q) / (1 + q): the argument of expf is exact and <= 0; exactly 1 or 0 once q
+ *            underflows to 0: never a NaN.
+ * mmrec_posterior_fusion_fwd_f32: the main launch and the finish; the ten tables read once, Z and score written once.
+ * mmrec_posterior_fusion_bwd_f32: ONE launch, given gZ [4, n, 64] (NULL: zeros) and g_kl [4] ON THE DEVICE (NULL: zeros; never
+ *   read by the host).  Every intermediate above is RECOMPUTED from the ten inputs: the state between the two calls is the inputs.
+ *   Per element, with ck = g_kl[k] inv_n and gz = gZ[k]:
+ *   up_k     gm_k = fma(ck, mu_k, gz);   gl_k = l_k <= 10 ? fma(gz, (0.05 E_k) sd_k, -((0.5 ck) (1 - el_k))) : 0
+ *            (l_k == 10 passes the gradient, as at::clamp's backward does; above 10 it is exactly 0; noise NULL: E_k = 0)
+ *   PoE backward of (gm, gl), the gradients of (m, l), into expert a (b alike):   w_a = ((T_a T_a) E_a) var,
+ *            d mu_a = (gm T_a) var,   d l_a = -(w_a fma(gm, mu_a - m, -gl))
+ *   stage 2 from up_p gives (g m1, g l1) and c's share; stage 1 from (g m1, g l1) gives v's and t's shares;
+ *   d_mu_k = share + gm_k,  d_lv_k = share + gl_k  for k in (v, t, c).
+ *   Any of the six outputs may be NULL (not computed); all six NULL: 0, no launch.  A wanted gradient with gZ and g_kl both NULL
+ *   is written as zeros.
+ * NO ATOMICS, every order fixed by n alone: two calls on the same inputs give the same bits.
+ * workspace: mmrec_posterior_fusion_workspace_bytes(n) = 16 blocks bytes (16 KB at most; 0 for n < 0 or n > 2^30), needed by the
+ * forward only.  Outputs must not alias inputs.
+ * d != 64, n < 0 or n > 2^30: MMREC_ERR_BAD_ARG; n == 0: 0, no launch, nothing written; a NULL input, some but not all of the
+ * four noise pointers, a NULL Z, score, kl or workspace in the forward: MMREC_ERR_BAD_ARG -- in this order, before any pointer
+ * is followed.  No synchronisation, no allocation, no data-dependent launch shape, capture-safe. */
+int32_t mmrec_posterior_fusion_rows_per_block(int64_t n);
+size_t mmrec_posterior_fusion_workspace_bytes(int64_t n);
+int mmrec_posterior_fusion_fwd_f32(const float* mu_v, const float* lv_v, const float* mu_t, const float* lv_t, const float* mu_c,
+                                   const float* lv_c, const float* E_p, const float* E_v, const float* E_t, const float* E_c,
+                                   int64_t n, int32_t d, float* Z, float* score, float* kl, void* workspace,
+                                   mmrec_stream_t stream);
+int mmrec_posterior_fusion_bwd_f32(const float* mu_v, const float* lv_v, const float* mu_t, const float* lv_t, const float* mu_c,
+                                   const float* lv_c, const float* E_p, const float* E_v, const float* E_t, const float* E_c,
+                                   const float* gZ, const float* g_kl, int64_t n, int32_t d, float* d_mu_v, float* d_lv_v,
+                                   float* d_mu_t, float* d_lv_t, float* d_mu_c, float* d_lv_c, mmrec_stream_t stream);
+
 /* Top-k of a mix of three row softmaxes against three whole tables, never storing a [B, N] block: DAMRS's pseudo-labels.
  * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
  * replaces: topk(p_a + p_b + 2 p_m, 10) with p = softmax(normalize(h[ids]) @ normalize(h).T, dim=1) for each of three

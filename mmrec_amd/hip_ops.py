@@ -3093,6 +3093,109 @@ def modal_fusion(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
 
 
 # ------------------------------------------------------------------------------------------------
+# MVGAE's posterior tail (csrc/posterior.hip): two products of experts, four reparametrisations, four KL terms, sigmoid(mu)
+# ------------------------------------------------------------------------------------------------
+POSTERIOR_FUSION = True   # False: every posterior_fusion call is `posterior_fusion_torch` (A/B runs)
+POSTERIOR_MAX_LOGVAR = 10
+
+
+def posterior_fusion_rows_per_block(n):
+    """rows of a table of n rows that one workgroup of the posterior fusion kernels walks (the library's plan)"""
+    return int(_lib.load().mmrec_posterior_fusion_rows_per_block(int(n)))
+
+
+def posterior_fusion_torch(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise=None):
+    """MVGAE.forward / calculate_loss's posterior tail (models/mvgae.py, the `fused_posterior` key off) as a function of the six
+    encoder outputs and the four noise tables (pd, v, t, c; None: z = mu): the operations of `product_of_experts`, `reparametrize`
+    and `kl_loss` in the model's order -> (Z [4, n, d], kl [4], score [n, d]).  The composition `posterior_fusion` falls back to."""
+    def poe(mu, logvar, eps=1e-8):
+        T = 1.0 / (torch.exp(logvar) + eps)
+        pd_var = 1.0 / torch.sum(T, dim=0)
+        return torch.sum(mu * T, dim=0) * pd_var, torch.log(pd_var)
+
+    def reparametrize(mu, logvar, e):
+        logvar = logvar.clamp(max=POSTERIOR_MAX_LOGVAR)
+        return mu if e is None else mu + e * 0.1 * torch.exp(logvar.mul(0.5))
+
+    def kl(mu, logvar):
+        logvar = logvar.clamp(max=POSTERIOR_MAX_LOGVAR)
+        return -0.5 * torch.mean(torch.sum(1 + logvar - mu ** 2 - logvar.exp(), dim=1))
+    pd_mu, pd_lv = poe(torch.stack([mu_v, mu_t]), torch.stack([lv_v, lv_t]))
+    pd_mu, pd_lv = poe(torch.stack([pd_mu, mu_c]), torch.stack([pd_lv, lv_c]))
+    pairs = ((pd_mu, pd_lv), (mu_v, lv_v), (mu_t, lv_t), (mu_c, lv_c))
+    es = (None,) * 4 if noise is None else noise
+    Z = torch.stack([reparametrize(m, l, e) for (m, l), e in zip(pairs, es)])
+    return Z, torch.stack([kl(m, l) for m, l in pairs]), torch.sigmoid(pd_mu).detach()
+
+
+def posterior_fusion_served(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise=None):
+    """True where `posterior_fusion` runs the kernels: six device fp32 contiguous [n, 64] tables of one shape on one device,
+    1 <= n <= 2^30, the noise None or four more such tables, the `POSTERIOR_FUSION` switch on."""
+    def table(t):
+        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
+    tabs = (mu_v, lv_v, mu_t, lv_t, mu_c, lv_c)
+    if noise is not None:
+        if not isinstance(noise, (tuple, list)) or len(noise) != 4:
+            return False
+        tabs = tabs + tuple(noise)
+    if not (POSTERIOR_FUSION and all(table(t) for t in tabs)):
+        return False
+    return bool(all(t.shape == mu_v.shape and t.device == mu_v.device for t in tabs))
+
+
+class _PosteriorFusion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, *ops):
+        lib = _lib.load()
+        mu_v = ops[0]
+        n = mu_v.shape[0]
+        Z = torch.empty((4,) + tuple(mu_v.shape), dtype=mu_v.dtype, device=mu_v.device)
+        score = torch.empty_like(mu_v)
+        kl = torch.empty(4, dtype=mu_v.dtype, device=mu_v.device)
+        ptrs = [_p(t) for t in ops] + [None] * (10 - len(ops))
+        ws = _ws(lib.mmrec_posterior_fusion_workspace_bytes(n), mu_v.device)
+        _lib.check(lib.mmrec_posterior_fusion_fwd_f32(*ptrs, n, EMB_DIM, _p(Z), _p(score), _p(kl), _p(ws), _stream()),
+                   "posterior_fusion_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*ops)                                  # every intermediate is recomputed: nothing else is kept
+        ctx.mark_non_differentiable(score)
+        return Z, kl, score
+
+    @staticmethod
+    def backward(ctx, gZ, g_kl, _g_score):
+        ops = ctx.saved_tensors
+        want = ctx.needs_input_grad[:6]
+        if not any(want) or (gZ is None and g_kl is None):
+            return (None,) * len(ops)
+        n = ops[0].shape[0]
+        gZ = None if gZ is None else gZ.contiguous()
+        g_kl = None if g_kl is None else g_kl.contiguous()
+        grads = [torch.empty_like(t) if w else None for t, w in zip(ops[:6], want)]
+        ptrs = [_p(t) for t in ops] + [None] * (10 - len(ops))
+        _lib.check(_lib.load().mmrec_posterior_fusion_bwd_f32(*ptrs, _p(gZ), _p(g_kl), n, EMB_DIM, *[_p(g) for g in grads],
+                                                              _stream()), "posterior_fusion_bwd")
+        return tuple(grads) + (None,) * (len(ops) - 6)
+
+
+def posterior_fusion(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise=None):
+    """MVGAE's posterior tail (mvgae.py, forward / calculate_loss) -> (Z [4, n, 64], kl [4], score [n, 64]):
+    (m1, l1) = PoE(v, t), (mu_p, l_p) = PoE((m1, l1), c) with PoE's T = 1 / (exp(l) + 1e-8), var = 1 / sum T, m = var sum mu T,
+    l = log var;  for k in (p, v, t, c): Z[k] = mu_k + 0.1 noise[k] exp(0.5 min(l_k, 10)) (noise None: Z[k] = mu_k),
+    kl[k] = -0.5 mean_rows sum_cols (1 + lh_k - mu_k^2 - exp(lh_k));  score = sigmoid(mu_p), without a gradient.  Differentiable
+    in the six encoder outputs; the noise gets none.
+    Served by the kernels (`posterior_fusion_served`): two launches forward (the main pass and the finish that adds the blocks'
+    KL partials in a fixed order), one backward; the ten tables read once, every output written once, every intermediate
+    RECOMPUTED in the backward, so the state between the calls is the inputs.  An operand that needs no gradient is not
+    computed.  No atomics: the same bits every call, so `DETERMINISTIC` changes nothing.  Supported domain: finite inputs with
+    |log-variance| <= 30 (include/mmrec_hip.h).
+    EVERY OTHER CASE (CPU tensors, a width other than 64, other dtypes, non-contiguous operands, an empty table, the switch
+    off) is `posterior_fusion_torch` with stock autograd."""
+    if posterior_fusion_served(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise):
+        return _PosteriorFusion.apply(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, *(noise or ()))
+    return posterior_fusion_torch(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise)
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

@@ -19,6 +19,15 @@ Reference quirks kept on purpose:
   * linear_layer1 / linear_layer2 feed an `x_hat` that is dropped when `concate` is False: they exist (and are saved)
     but receive no gradient;
   * evaluation scores with sigmoid(mu) of the LAST training forward.
+
+Everything after the three encoders -- two products of experts, four reparametrisations, four KL terms, four full-table
+sigmoids and sigmoid(mu) for the evaluation table -- is, by default, a composition of about 140 element-wise launches
+over [users + items, 64] temporaries, mirrored by autograd.  With the config key `fused_posterior: True` (absent /
+False: that path, untouched) `calculate_loss` makes one `hip_ops.posterior_fusion` call (csrc/posterior.hip: two
+launches forward, one backward, every intermediate recomputed) for the four z tables, the four KL terms and
+`result_embed`; the four noise tables are drawn in the composition's order (pd, v, t, c); and the four reconstruction
+terms become one batched term: the 3 B rows of cat(user, pos, neg) are gathered from the four z tables FIRST, the sigmoid
+runs on those [4, 3 B, 64] rows only, then one bmm and one row maximum.  The loss is the same sum.
 """
 import math
 
@@ -124,6 +133,7 @@ class MVGAE(FusedEvalMixin, GeneralRecommender):
         self.num_user, self.num_item = self.n_users, self.n_items
         self.dim_x = config['embedding_size']
         self.beta = config['beta']
+        self.fused_posterior = bool(config['fused_posterior']) if 'fused_posterior' in config else False    # new key, default off
         num_layer = config['n_layers']
         if self.v_feat is None or self.t_feat is None:
             raise ValueError("MVGAE needs image and text features (its forward reads both encoders)")
@@ -174,8 +184,26 @@ class MVGAE(FusedEvalMixin, GeneralRecommender):
         logvar = logvar.clamp(max=MAX_LOGVAR)
         return -0.5 * torch.mean(torch.sum(1 + logvar - mu ** 2 - logvar.exp(), dim=1))
 
+    def _fused_loss(self, user, pos_items, neg_items):
+        """calculate_loss with the `fused_posterior` key on: the same sum, the posterior tail as one op"""
+        v_mu, v_logvar = self.v_gcn(self.graph)
+        t_mu, t_logvar = self.t_gcn(self.graph)
+        c_mu, c_logvar = self.c_gcn(self.graph)
+        ops = [t.contiguous() for t in (v_mu, v_logvar, t_mu, t_logvar, c_mu, c_logvar)]
+        noise = [torch.randn_like(ops[1]) for _ in range(4)] if self.training else None     # the composition's order: pd, v, t, c
+        z, kl, self.result_embed = hip_ops.posterior_fusion(*ops, noise)
+        b = user.shape[0]
+        rows = torch.sigmoid(z.index_select(1, torch.cat((user, pos_items, neg_items))))    # [4, 3 B, 64]
+        zu, zp, zn = rows[:, :b], rows[:, b:2 * b], rows[:, 2 * b:]
+        pos = torch.sigmoid((zu * zp).sum(dim=2))
+        hardest = torch.bmm(zu, zn.transpose(1, 2)).max(dim=-1).values                      # [4, B]
+        recon = -torch.sum(torch.log2(torch.sigmoid(pos - torch.sigmoid(hardest))))
+        return recon + self.beta * kl.sum()
+
     def calculate_loss(self, interaction):
         user, pos_items, neg_items = interaction[0], interaction[1], interaction[2]
+        if self.fused_posterior:
+            return self._fused_loss(user, pos_items, neg_items)
         pd_mu, pd_logvar, z, v_mu, v_logvar, t_mu, t_logvar, c_mu, c_logvar = self.forward()
         z_v = self.reparametrize(v_mu, v_logvar)
         z_t = self.reparametrize(t_mu, t_logvar)

@@ -11,23 +11,25 @@
 // 16-B LDS read feeds 4 MFMAs, and A/B use the same permutation, so the product is unchanged.
 // All split partial sums are combined in a fixed order (no float atomics): deterministic.
 
+//
+// Which kernel serves which shape (out = 64 unless said; "big" = X larger than 192 MiB, which does not stay in the 256 MB
+// Infinity Cache and is streamed non-temporally, template argument NT; G = rows gathered through ids, mmrec_linear_rows_*, which
+// asks for F % 128 == 0):
+//   forward, fp32 (mmrec_linear_fwd_f32)        F % 32 == 0: linear_fwd_dma_kernel<big, G>; other F % 4 == 0: linear_fwd_kernel<0>;
+//                                               more than one k chunk: + slab_reduce_kernel
+//   forward, split (mmrec_linear_fwd_split_f32) F % 32 == 0: linear_w_split_kernel, linear_fwd_dma_f16x3_kernel<big, G> (big: the
+//                                               rotated k walk), slab_reduce_kernel if chunked, then linear_fwd_dma_kernel<big, G>
+//                                               over the flagged row blocks; other F: the fp32 forward
+//   backward, split (mmrec_linear_bwd_split_f32) F % 128 == 0: bwd_prep_kernel (dW and dX wanted; else bwd_dy_split_kernel /
+//                                               bwd_wt_split_kernel), linear_bwd_w_v2_kernel<big, G>, bwd_w_finish_kernel,
+//                                               bwd_x_f16x3_kernel<0>; other F or out > 64: the two fp32 calls below
+//   dW, fp32 (mmrec_linear_bwd_w_f32)           any F % 4 == 0, out = 64 z (grid.z = z): linear_bwd_w_dma_kernel, or
+//                                               linear_bwd_w_kernel when an item chunk of X or dY passes 2^31 bytes;
+//                                               + slab_reduce_kernel if chunked, db_reduce_kernel if db is wanted
+//   dX, fp32 (mmrec_linear_bwd_x_f32)           F % 128 == 0: gemm64_stream_kernel (mfma_stream.h); other F: linear_bwd_x_kernel
+//   any width (mmrec_gemm_nt_f32)               the 128 x 128 kernels of mfma_stream.h
 
-// tools/gemm_probe.hip builds the forward kernel with an ablation bit mask (see linear_fwd_kernel);
-// the library only ever uses 0.
-#ifndef MMREC_GEMM_PROBE_MODE
-#define MMREC_GEMM_PROBE_MODE 0
-#endif
-#define MMREC_STREAM_PROBE MMREC_GEMM_PROBE_MODE
 #include "mfma_stream.h"
-#ifndef MMREC_GEMM_LEGACY_FWD
-#define MMREC_GEMM_LEGACY_FWD 0   // probe: force the register-staged forward for every F
-#endif
-#ifndef MMREC_FWD_ROT
-#define MMREC_FWD_ROT 11         // split-operand forward over an X streamed from HBM: row block b starts its k walk at tile (b * ROT) % T of its chunk (0 = every block at tile 0)
-#endif
-#ifndef MMREC_GEMM_DYN_LDS
-#define MMREC_GEMM_DYN_LDS 0   // probe: extra dynamic LDS per workgroup, caps workgroups per CU
-#endif
 
 namespace {
 
@@ -38,10 +40,9 @@ constexpr int LIN_XP = LIN_BM / LIN_RPP, LIN_WP = 64 / LIN_RPP;
 constexpr int BW_BF_ZERO = 128;             // floats of g_zero_row: one 128-column segment of a dW tile row (the forward reads 32)
 
 // ---------------------------------------------------------------------------------------- forward
-// grid (ceil(n/128), ksplit); wave w owns rows w*32..+31 and all 64 outputs (2 accumulators).
-// ABL (tools/gemm_probe.hip only; the library uses 0): bit0 no streaming global loads, bit1 no LDS
-// stores after the first tile, bit2 no barriers after the first tile, bit3 LDS fragments read once.
-template <int ABL>
+// grid (ceil(n/128), ksplit); wave w owns rows w*32..+31 and all 64 outputs (2 accumulators).  Operands staged through registers:
+// the forward for an F that is no multiple of 32.
+template <int = 0>      // (only for the kernel's printed name, linear_fwd_kernel<0>, which the committed profiles carry)
 __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict__ X,
                                                          const float* __restrict__ W,
                                                          const float* __restrict__ bias,
@@ -77,16 +78,13 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
         }
     };
     for (int k0 = kb; k0 < ke; k0 += LIN_BK) {
-        const bool first = k0 == kb;
-        if (!(ABL & 2) || first) {
 #pragma unroll
-            for (int p = 0; p < LIN_XP; ++p) *reinterpret_cast<float4*>(&Xs[lr + LIN_RPP * p][lq]) = xr[p];
+        for (int p = 0; p < LIN_XP; ++p) *reinterpret_cast<float4*>(&Xs[lr + LIN_RPP * p][lq]) = xr[p];
 #pragma unroll
-            for (int p = 0; p < LIN_WP; ++p) *reinterpret_cast<float4*>(&Ws[lr + LIN_RPP * p][lq]) = wr[p];
-        }
-        if (!(ABL & 4) || first) __syncthreads();
-        if (k0 + LIN_BK < ke && !(ABL & 1)) gload(k0 + LIN_BK);  // next tile in flight under the MFMAs
-        if (!(ABL & 8) || first) frags();
+        for (int p = 0; p < LIN_WP; ++p) *reinterpret_cast<float4*>(&Ws[lr + LIN_RPP * p][lq]) = wr[p];
+        __syncthreads();
+        if (k0 + LIN_BK < ke) gload(k0 + LIN_BK);  // next tile in flight under the MFMAs
+        frags();
 #pragma unroll
         for (int k8 = 0; k8 < LIN_BK / 8; ++k8) {
             const float4 a = fa[k8], b0 = fb0[k8], b1 = fb1[k8];
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
             acc0 = mfma32(a.z, b0.z, acc0); acc1 = mfma32(a.z, b1.z, acc1);
             acc0 = mfma32(a.w, b0.w, acc0); acc1 = mfma32(a.w, b1.w, acc1);
         }
-        if (!(ABL & 4)) __syncthreads();
+        __syncthreads();
     }
     // out = Y (+bias) when gridDim.y == 1, else partial slab blockIdx.y of the workspace
     float* dst = out + (size_t)blockIdx.y * n * 64;
@@ -155,6 +153,40 @@ __device__ __forceinline__ void fwd_row_sources(const float* __restrict__ T, con
     }
 }
 
+// ------------------------------------------------------------------- the three-stage LDS-DMA ring
+// The walk of the kernels that bring both operand tiles by LDS-DMA: T tiles through ring stages 0, 1, 2, ONE barrier per tile, the
+// copies of tile t + 2 in flight under the MFMAs of tile t.  issue(stage, t) starts this wave's copies of tile t into a stage -- SIX
+// per wave and tile in every user (4 + 2), which is what the vmcnt below counts on; compute(stage) multiplies the tile in a stage.
+// linear_fwd_dma_kernel and linear_bwd_w_dma_kernel walk it; linear_fwd_dma_f16x3_kernel, at its 256-VGPR ceiling, keeps the same
+// walk written out (through this function its forward measured 2 % slower at Amazon-Baby size: EXPERIMENTS.md).
+// A stage arrives as a std::integral_constant, so that the kernel names its LDS arrays itself (ring_stage): with the stage
+// pointers handed through this function the fragment reads were no longer paired into ds_read2 (+184 instructions, +38 VGPRs in
+// linear_bwd_w_dma_kernel).
+template <int S>
+__device__ __forceinline__ float* ring_stage(std::integral_constant<int, S>, float* s0, float* s1, float* s2) {
+    return S == 0 ? s0 : S == 1 ? s1 : s2;
+}
+template <class Issue, class Compute>
+__device__ __forceinline__ void dma_ring3(int T, Issue issue, Compute compute) {
+    constexpr std::integral_constant<int, 0> s0{};
+    constexpr std::integral_constant<int, 1> s1{};
+    constexpr std::integral_constant<int, 2> s2{};
+    // one step: tile t sits in stage `cur`; `nxt` is the stage tile t - 1 used, now free
+    auto step = [&](auto cur, auto nxt, int t) {
+        if (t + 1 < T) MMREC_WAIT_VM(6); else MMREC_WAIT_VM(0);  // my pieces of tile t have landed
+        __builtin_amdgcn_s_barrier();                            // everyone's have; tile t - 1 is consumed
+        if (t + 2 < T) issue(nxt, t + 2);
+        compute(cur);
+    };
+    if (T > 0) issue(s0, 0);
+    if (T > 1) issue(s1, 1);
+    for (int t = 0; t < T;) {
+        step(s0, s2, t); if (++t >= T) break;
+        step(s1, s0, t); if (++t >= T) break;
+        step(s2, s1, t); ++t;
+    }
+}
+
 // ------------------------------------------------------------------- forward, LDS-DMA pipeline
 // Same tile (128 x 64 per workgroup, wave w owns rows 32w..+31) but the operands go HBM -> LDS with
 // `buffer_load_dwordx4 ... lds` (no staging VGPRs, no address VALU: scalar k offset + per-lane
@@ -164,14 +196,14 @@ __device__ __forceinline__ void fwd_row_sources(const float* __restrict__ T, con
 // applied on the source side: 16-B chunk c of row r lives at position c ^ ((r >> 1) & 7), which makes
 // every 16-lane service group of ds_read_b128 ({0-3,12-15,20-27}, ...) cover all 64 banks.
 // Requires F % 32 == 0 (4096, 384, 4480 all are); other F take linear_fwd_kernel.
-constexpr int DM_BK = 32, DM_STAGES = 3;
+constexpr int DM_BK = 32;
 template <bool NT, bool G = false>     // G: X is a table and row j of the operand is X[ids[j]] (see "gathered operand rows")
 __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __restrict__ X,
                                                                 const float* __restrict__ W,
                                                                 const float* __restrict__ bias,
                                                                 float* __restrict__ out, int n, int F,
                                                                 int k_chunk, const int* __restrict__ redo,
-                                                                const int64_t* __restrict__ ids = nullptr, int64_t n_table = 0) {
+                                                                const int64_t* __restrict__ ids, int64_t n_table) {
     __shared__ __attribute__((aligned(1024))) float Xs0[LIN_BM * DM_BK], Xs1[LIN_BM * DM_BK], Xs2[LIN_BM * DM_BK];
     __shared__ __attribute__((aligned(1024))) float Ws0[64 * DM_BK], Ws1[64 * DM_BK], Ws2[64 * DM_BK];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -183,8 +215,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __r
     const int kb = blockIdx.y * k_chunk, ke = min(kb + k_chunk, F);
     const int T = (ke - kb) / DM_BK;
     const int rows_left = min(LIN_BM, n - m0);
-    // probe bit 4: every workgroup streams the same 128 rows (L2 resident) instead of its own
-    const i32x4 rx = raw_rsrc(X + ((MMREC_GEMM_PROBE_MODE & 16) || G ? 0 : (size_t)m0 * F), G ? 0u : (unsigned)rows_left * (unsigned)F * 4u);
+    const i32x4 rx = raw_rsrc(X + (G ? 0 : (size_t)m0 * F), G ? 0u : (unsigned)rows_left * (unsigned)F * 4u);
     const i32x4 rw = raw_rsrc(W, 64u * (unsigned)F * 4u);
     // per-lane source offsets of this wave's pieces (4 of X, 2 of W), swizzle on the source side
     int vx[4], vw[2];
@@ -201,7 +232,8 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __r
         const int r = 16 * wave + 8 * j + (lane >> 3);
         vw[j] = r * F * 4 + (((lane & 7) ^ ((r >> 1) & 7)) << 4);
     }
-    auto issue = [&](float* xs, float* ws, int t) {
+    auto issue = [&](auto stage, int t) {
+        float *xs = ring_stage(stage, Xs0, Xs1, Xs2), *ws = ring_stage(stage, Ws0, Ws1, Ws2);
         const int so = (kb + t * DM_BK) * 4;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -209,17 +241,16 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __r
             else lds_dma16<NT>(rx, lds_addr(xs + (4 * wave + j) * 256), vx[j], so);
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j)   // probe bit 5: W only for the first two tiles
-            if (!(MMREC_GEMM_PROBE_MODE & 32) || t < 2) lds_dma16<false>(rw, lds_addr(ws + (2 * wave + j) * 256), vw[j], so);
+        for (int j = 0; j < 2; ++j) lds_dma16<false>(rw, lds_addr(ws + (2 * wave + j) * 256), vw[j], so);
     };
     const int i = lane & 31, h = lane >> 5, g = (i >> 1) & 7;
     int ko[4];  // float offset of this lane's 16-B chunk within a row, per k8
 #pragma unroll
     for (int k8 = 0; k8 < 4; ++k8) ko[k8] = ((2 * k8 + h) ^ g) << 2;
     f32x16 acc0 = {0}, acc1 = {0};
-    auto compute = [&](const float* xs, const float* ws) {
-        const float* xa = xs + (32 * wave + i) * DM_BK;
-        const float* wb = ws + i * DM_BK;
+    auto compute = [&](auto stage) {
+        const float* xa = ring_stage(stage, Xs0, Xs1, Xs2) + (32 * wave + i) * DM_BK;
+        const float* wb = ring_stage(stage, Ws0, Ws1, Ws2) + i * DM_BK;
         float4 fa[4], fb0[4], fb1[4];
 #pragma unroll
         for (int k8 = 0; k8 < 4; ++k8) {
@@ -236,20 +267,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __r
             acc0 = mfma32(a.w, b0.w, acc0); acc1 = mfma32(a.w, b1.w, acc1);
         }
     };
-    // one pipeline step: tile t sits in (xc, wc); (xn, wn) is the stage tile t-1 used, now free
-    auto step = [&](const float* xc, const float* wc, float* xn, float* wn, int t) {
-        if (t + 1 < T && !(MMREC_GEMM_PROBE_MODE & 32)) MMREC_WAIT_VM(6); else MMREC_WAIT_VM(0);  // my pieces of tile t have landed
-        __builtin_amdgcn_s_barrier();                            // everyone's have; tile t-1 is consumed
-        if (t + 2 < T && !((MMREC_GEMM_PROBE_MODE & 64) && t >= 2)) issue(xn, wn, t + 2);  // probe bit 6: no loads
-        compute(xc, wc);
-    };
-    if (T > 0) issue(Xs0, Ws0, 0);
-    if (T > 1) issue(Xs1, Ws1, 1);
-    for (int t = 0; t < T;) {
-        step(Xs0, Ws0, Xs2, Ws2, t); if (++t >= T) break;
-        step(Xs1, Ws1, Xs0, Ws0, t); if (++t >= T) break;
-        step(Xs2, Ws2, Xs1, Ws1, t); ++t;
-    }
+    dma_ring3(T, issue, compute);
     float* dst = out + (size_t)blockIdx.y * n * 64;
     const float b0 = (bias && gridDim.y == 1) ? bias[i] : 0.f;
     const float b1 = (bias && gridDim.y == 1) ? bias[32 + i] : 0.f;
@@ -289,6 +307,19 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_kernel(const float* __r
 typedef __attribute__((ext_vector_type(8))) _Float16 g_half8;
 
 constexpr float SPLIT_ROW_MIN = 0x1p-10f;    // a row (of X or W) whose largest |element| is below this, and not 0, is recomputed in fp32
+// Row block b of the split forward over an X streamed from HBM starts its k walk at tile (b * FWD_ROT) % T of its chunk (see the
+// kernel; 0, 5, 7, 11, 13 in profiles/r06_linear_fwd_rotation_and_splits.log).
+constexpr int FWD_ROT = 11;
+
+// the only hi / lo' split: x = hi + 2^-11 lo' with hi = fp16(x), lo' = fp16(2^11 (x - hi))
+__device__ __forceinline__ void split8(const float (&x)[8], g_half8& hi, g_half8& lo) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const _Float16 h = (_Float16)x[e];
+        hi[e] = h;
+        lo[e] = (_Float16)((x[e] - (float)h) * 2048.f);
+    }
+}
 
 // grid 64 (one workgroup per W row): a thread splits 8 consecutive floats at a time (two 16-B loads, coalesced across the
 // workgroup) into 8 hi halves + 8 lo' halves of the row's tile layout; redo[0 .. nblocks) = 0 (workgroup 0),
@@ -306,12 +337,9 @@ __global__ __launch_bounds__(256) void linear_w_split_kernel(const float* __rest
         const float4 a = src[0], b = src[1];
         const float w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         g_half8 hi, lo;
+        split8(w, hi, lo);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            hi[k] = (_Float16)w[k];
-            lo[k] = (_Float16)((w[k] - (float)hi[k]) * 2048.f);
-            mx = fmaxf(mx, fabsf(w[k]));
-        }
+        for (int k = 0; k < 8; ++k) mx = fmaxf(mx, fabsf(w[k]));
         _Float16* dst = reinterpret_cast<_Float16*>(Wsp + (size_t)row * F + kb * 32);
         *reinterpret_cast<g_half8*>(dst + sub) = hi;
         *reinterpret_cast<g_half8*>(dst + 32 + sub) = lo;
@@ -333,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_f16x3_kernel(const floa
                                                                       float* __restrict__ out, int n, int F,
                                                                       int k_chunk, float* __restrict__ rowmax_part,
                                                                       int* __restrict__ redo,
-                                                                      const int64_t* __restrict__ ids = nullptr, int64_t n_table = 0) {
+                                                                      const int64_t* __restrict__ ids, int64_t n_table) {
     __shared__ __attribute__((aligned(1024))) float Xs0[LIN_BM * DM_BK], Xs1[LIN_BM * DM_BK], Xs2[LIN_BM * DM_BK];
     __shared__ __attribute__((aligned(1024))) float Ws0[64 * DM_BK], Ws1[64 * DM_BK], Ws2[64 * DM_BK];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -364,11 +392,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_f16x3_kernel(const floa
     // split count already made a function of n -- fp32-accurate either way (the tests' float64 comparisons).
     // Only for an X that is streamed from HBM (NT: larger than the Infinity Cache): against a cache-resident X the rotation
     // measured 1-2 us SLOWER (7,050 rows: 96.8 against 94.5 us forward + backward as a replay; 4,096 rows: +1.5 us).
-#if MMREC_FWD_ROT
-    const int rot = (NT && T > 0) ? (int)((blockIdx.x * (unsigned)MMREC_FWD_ROT) % (unsigned)T) : 0;
-#else
-    const int rot = 0;
-#endif
+    const int rot = (NT && T > 0) ? (int)((blockIdx.x * (unsigned)FWD_ROT) % (unsigned)T) : 0;
     auto issue = [&](float* xs, float* ws, int t) {
         int tt = t + rot;
         if (tt >= T) tt -= T;
@@ -394,12 +418,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_f16x3_kernel(const floa
             const float4 xa1 = *reinterpret_cast<const float4*>(xa + (((c0 + 1) ^ g) << 2));
             const float xv[8] = {xa0.x, xa0.y, xa0.z, xa0.w, xa1.x, xa1.y, xa1.z, xa1.w};
             g_half8 ah, al;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const _Float16 hi = (_Float16)xv[e];
-                ah[e] = hi;
-                al[e] = (_Float16)((xv[e] - (float)hi) * 2048.f);
-            }
+            split8(xv, ah, al);
 #pragma unroll
             for (int e = 0; e < 8; e += 2) xmax = fmaxf(fmaxf(xmax, fabsf(xv[e])), fabsf(xv[e + 1]));     // v_max3_f32 |.|, |.|
             const int ch = ((2 * st + h) ^ g) << 2, cl = ((4 + 2 * st + h) ^ g) << 2;     // hi / lo' chunks of the W tile row
@@ -453,19 +472,10 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_dma_f16x3_kernel(const floa
     }
 }
 
-// out[idx] = sum_s part[s][idx] (+ bias[idx % 64]) in slab order; total = n*64 (multiple of 4).
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ part, int nslab,
-                                                          size_t slab_elems,
-                                                          const float* __restrict__ bias,
-                                                          float* __restrict__ out,
-                                                          const float* __restrict__ rowmax_part = nullptr,
-                                                          int* __restrict__ redo = nullptr) {
-    const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i4 * 4 >= slab_elems) return;
-    part += (size_t)blockIdx.y * nslab * slab_elems;      // (grid.y > 1: the 64-output groups of a wide dW, each with its own slabs)
-    out += (size_t)blockIdx.y * slab_elems;
-    // four independent chains keep the slab loads in flight (a single chain of up to 64 dependent
-    // adds was latency bound: 17 us for a few MB); the combination order is still fixed
+// float4 i4 of sum_s part[s]: four independent chains keep the slab loads in flight (a single chain of up to 64 dependent adds
+// was latency bound: 17 us for a few MB); the order is fixed: slab s into chain s % 4, the remainder into chain 0, then
+// (t0 + t1) + (t2 + t3)
+__device__ __forceinline__ float4 slab_sum4(const float* part, int nslab, size_t slab_elems, size_t i4) {
     float4 t0 = f4_zero(), t1 = f4_zero(), t2 = f4_zero(), t3 = f4_zero();
     int s = 0;
     for (; s + 3 < nslab; s += 4) {
@@ -475,7 +485,21 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
         t3 = f4_add(t3, reinterpret_cast<const float4*>(part + (size_t)(s + 3) * slab_elems)[i4]);
     }
     for (; s < nslab; ++s) t0 = f4_add(t0, reinterpret_cast<const float4*>(part + (size_t)s * slab_elems)[i4]);
-    float4 t = f4_add(f4_add(t0, t1), f4_add(t2, t3));
+    return f4_add(f4_add(t0, t1), f4_add(t2, t3));
+}
+
+// out[idx] = sum_s part[s][idx] (+ bias[idx % 64]) in slab order; total = n*64 (multiple of 4).
+__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ part, int nslab,
+                                                          size_t slab_elems,
+                                                          const float* __restrict__ bias,
+                                                          float* __restrict__ out,
+                                                          const float* __restrict__ rowmax_part,
+                                                          int* __restrict__ redo) {
+    const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i4 * 4 >= slab_elems) return;
+    part += (size_t)blockIdx.y * nslab * slab_elems;      // (grid.y > 1: the 64-output groups of a wide dW, each with its own slabs)
+    out += (size_t)blockIdx.y * slab_elems;
+    float4 t = slab_sum4(part, nslab, slab_elems, i4);
     if (bias) t = f4_add(t, reinterpret_cast<const float4*>(bias)[i4 & 15]);
     reinterpret_cast<float4*>(out)[i4] = t;
     if (redo) {     // split-operand forward (64 columns = 16 threads per row): non-finite sums, rows of tiny magnitude -> redo in fp32
@@ -596,7 +620,8 @@ __global__ __launch_bounds__(256, 2) void linear_bwd_w_dma_kernel(const float* _
     for (int j = 0; j < 4; ++j) vx[j] = (2 * (4 * wave + j) + (lane >> 5)) * F * 4 + (lane & 31) * 16;
 #pragma unroll
     for (int j = 0; j < 2; ++j) vg[j] = (4 * (2 * wave + j) + (lane >> 4)) * ldg * 4 + (lane & 15) * 16;
-    auto issue = [&](float* gs, float* xs, int t) {
+    auto issue = [&](auto stage, int t) {
+        float *gs = ring_stage(stage, G0, G1, G2), *xs = ring_stage(stage, X0, X1, X2);
         const int sx = t * BW_BK * F * 4, sg = t * BW_BK * ldg * 4;
 #pragma unroll
         for (int j = 0; j < 4; ++j) lds_dma16<false>(rx, lds_addr(xs + (4 * wave + j) * 256), vx[j], sx);
@@ -607,7 +632,8 @@ __global__ __launch_bounds__(256, 2) void linear_bwd_w_dma_kernel(const float* _
     const bool do_db = dbpart && blockIdx.x == 0 && tid < 64;
     f32x16 acc0 = {0}, acc1 = {0};
     float dbacc = 0.f;
-    auto compute = [&](const float* gs, const float* xs) {
+    auto compute = [&](auto stage) {
+        const float *gs = ring_stage(stage, G0, G1, G2), *xs = ring_stage(stage, X0, X1, X2);
         if (do_db) {
 #pragma unroll
             for (int k = 0; k < BW_BK; ++k) dbacc += gs[k * 64 + tid];
@@ -620,20 +646,7 @@ __global__ __launch_bounds__(256, 2) void linear_bwd_w_dma_kernel(const float* _
             acc1 = mfma32(gs[k * 64 + 32 + i], b, acc1);
         }
     };
-    const int T = (rows + BW_BK - 1) / BW_BK;
-    auto step = [&](const float* gc, const float* xc, float* gn, float* xn, int t) {
-        if (t + 1 < T) MMREC_WAIT_VM(6); else MMREC_WAIT_VM(0);
-        __builtin_amdgcn_s_barrier();
-        if (t + 2 < T) issue(gn, xn, t + 2);
-        compute(gc, xc);
-    };
-    if (T > 0) issue(G0, X0, 0);
-    if (T > 1) issue(G1, X1, 1);
-    for (int t = 0; t < T;) {
-        step(G0, X0, G2, X2, t); if (++t >= T) break;
-        step(G1, X1, G0, X0, t); if (++t >= T) break;
-        step(G2, X2, G1, X1, t); ++t;
-    }
+    dma_ring3((rows + BW_BK - 1) / BW_BK, issue, compute);
     if (do_db) dbpart[blockIdx.y * 64 + tid] = dbacc;
     float* dst = part + (size_t)blockIdx.y * 64 * F;
     const int f = f0 + wave * 32 + i;
@@ -725,14 +738,6 @@ __global__ __launch_bounds__(256) void linear_bwd_x_kernel(const float* __restri
 //     holds the whole row), and one per COLUMN f of W, applied when W is written transposed + split (bwd_wt_split_kernel).
 // Inf / NaN anywhere give non-finite results as F.linear's backward does.
 // =====================================================================================================================
-__device__ __forceinline__ void split8(const float (&x)[8], g_half8& hi, g_half8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)x[e];
-        hi[e] = h;
-        lo[e] = (_Float16)((x[e] - (float)h) * 2048.f);
-    }
-}
 // exact power-of-two scale that brings a maximum magnitude `mx` into [2^target, 2^(target + 1)), and its inverse; 1 for
 // mx == 0 and for inf / NaN (which then propagate); clamped for maxima below 2^-100
 __device__ __forceinline__ void pow2_scale(float mx, int target, float& sc, float& inv) {
@@ -778,20 +783,32 @@ __global__ __launch_bounds__(256) void bwd_wt_split_kernel(const float* __restri
     bwd_wt_split_body(blockIdx.x, W, F, Wt_sp, wcs_inv);
 }
 
-// dW partial[o][f] over an item chunk on v_mfma_f32_32x32x16_bf16 with THREE-WAY split operands: every fp32 number is
-// b1 + b2 + b3 with b1 = bf16(x), b2 = bf16(x - b1), b3 = bf16(x - b1 - b2) -- 24 significand bits in three pieces that each
-// carry fp32's 8-bit exponent, so there is nothing to scale and nothing to guard: gradients of 1e-30 next to gradients of 1e-3
-// (a batch's BPR coefficients span 40 binades once pairs separate: measured on the Amazon-Sports-shaped FREEDOM step), features
-// of any magnitude, inf / NaN (non-finite in, non-finite out; an inf may come out as NaN: inf - bf16(inf) is NaN) all take the
-// same path.  x y = b1 c1 + (b1 c2 + b2 c1) + (b2 c2 + b1 c3 + b3 c1) + R, |R| <= 2^-22 |x y| (the three dropped products b2 c3,
-// b3 c2, b3 c3 are each below 2^-24 |x y|; the bound every statement of this file and of mmrec_hip.h uses): six products per 16 k (the fp16 form of
-// the forward takes three, eight fp32 MFMAs take 16 x the time), one fp32 accumulator set, smallest products first.
-// The FIRST form of this kernel used the forward's two fp16 halves with one power-of-two scale per column of dY and a range
-// guard; real gradient columns leave any single scale's range within an epoch (guard at 2^26: fired on most steps, at 2^30: on
-// 16 % of the steps of epoch 0 and rising), each time sending dW to a slow fix-up -- profiles/r05_run_configs.log.
-// Structure: linear_bwd_w_dma_kernel's (both operand tiles by LDS-DMA in their natural item-major layout, 3-stage ring, fused
-// bias-gradient partials); X is split in registers by the wave that multiplies it, dY -- wanted by every wave -- once per
-// workgroup into LDS fragments one tile ahead (the split is ~6 VALU per element).
+// ---- dW on v_mfma_f32_32x32x16_bf16 with THREE-WAY split operands: bwd_dy_split_kernel + linear_bwd_w_v2_kernel -------------
+// Number format.  Every fp32 number is b1 + b2 + b3 with b1 = bf16(x), b2 = bf16(x - b1), b3 = bf16(x - b1 - b2): 24 significand
+// bits in three pieces that each carry fp32's 8-bit exponent, so there is nothing to scale and nothing to guard.  Gradients of
+// 1e-30 next to gradients of 1e-3 (a batch's BPR coefficients span 40 binades once pairs separate: measured on the
+// Amazon-Sports-shaped FREEDOM step), features of any magnitude, inf / NaN (non-finite in, non-finite out; an inf may come out as
+// NaN: inf - bf16(inf) is NaN) all take the same path.
+//     x y = b1 c1 + (b1 c2 + b2 c1) + (b2 c2 + b1 c3 + b3 c1) + R,      |R| <= 2^-22 |x y|
+// (the three dropped products b2 c3, b3 c2, b3 c3 are each below 2^-24 |x y|; 2^-22 is the bound every statement of this file and
+// of mmrec_hip.h uses): six products per 16 k (the fp16 form of the forward takes three, eight fp32 MFMAs take 16 x the time) into
+// ONE fp32 accumulator set, smallest products first: b3 c1, b1 c3, b2 c2, b2 c1, b1 c2, b1 c1.
+// Why not the forward's two fp16 halves: that form needs one power-of-two scale per column of dY and a range guard, and real
+// gradient columns leave any single scale's range within an epoch (guard at 2^26: fired on most steps, at 2^30: on 16 % of the
+// steps of epoch 0 and rising), each time sending dW to a slow fix-up -- profiles/r05_run_configs.log.
+// Structure.  The dY side is split ONCE PER CALL, the X side in registers by the wave that multiplies it:
+//   bwd_dy_split_kernel      dY -> the three bf16 parts of every 32-item tile, ALREADY in MFMA A-fragment layout (12 KB per tile,
+//                            [2 kstep + otile][part][lane] x 16 B), + the bias gradient's partial sums (one per workgroup, fixed
+//                            order, free of atomics);
+//   linear_bwd_w_v2_kernel   X tiles by LDS-DMA (3-stage ring, natural item-major layout) AND the ready-made A fragments by
+//                            LDS-DMA (linear 12-KB copies: no VALU, no LDS write, nothing between barrier and MFMAs but the X
+//                            split, ~6 VALU per element); 72 KB of LDS, so TWO workgroups share a CU and one's barrier wait runs
+//                            under the other's MFMAs.  Eight waves: wave w multiplies k-step (w >> 2) of every tile into its own
+//                            accumulators for the 32 columns (w & 3); the two k-step halves are added through LDS at the end.
+// History: the round-5 kernel split dY in every one of the F / 128 column-block workgroups through an LDS round trip between the
+// tile's barrier and its MFMAs (39 us at Amazon-Baby size, X at 2.9 TB/s, MFMA pipe busy 30 %; its eight-wave form and its ring
+// depths in profiles/r05_linear_bwd_w_bf16x3_ab.log); this one, its A-fragment ring of two against three tiles and its
+// workgroups per CU in profiles/r06_linear_bwd_w_v2_ab.log.  Same six products in the same order: the two give the same dW bits.
 typedef __attribute__((ext_vector_type(8))) __bf16 g_bf8;
 __device__ __forceinline__ void split3(const float (&x)[8], g_bf8& p1, g_bf8& p2, g_bf8& p3) {
 #pragma unroll
@@ -805,175 +822,9 @@ __device__ __forceinline__ void split3(const float (&x)[8], g_bf8& p1, g_bf8& p2
     }
 }
 
-// Eight waves, two per SIMD: wave w multiplies k-step (w >> 2) of every 32-item tile into its own accumulators for the 32 columns
-// (w & 3); the two k-step halves are added through LDS at the end.  (With four waves -- one per SIMD running its LDS reads, ~170
-// VALU and 24 MFMAs per tile back to back -- the kernel took 39.9 us at Amazon-Baby size; with two per SIMD one wave's MFMAs run
-// under the other's split: -3.4 us forward + backward at Baby size, -15 us at Sports size, profiles/r05_linear_bwd_w_bf16x3_ab.log.)
-#ifndef MMREC_BWD_W_STAGES
-#define MMREC_BWD_W_STAGES 3     // X tiles in the LDS ring (S - 1 in flight per workgroup); 4, 5, 6 measured 1 ... 2 us slower at Amazon-Baby size: profiles/r05_linear_bwd_w_bf16x3_ab.log
-#endif
-typedef __attribute__((ext_vector_type(4))) __bf16 g_bf4;
-template <bool NT>     // NT: X does not fit the Infinity Cache and is read once per call: streamed non-temporal (as in the forward)
-__global__ __launch_bounds__(512) void linear_bwd_w_bf16x3_kernel(const float* __restrict__ dY, const float* __restrict__ X,
-                                                                  float* __restrict__ part, float* __restrict__ dbpart, int n, int F,
-                                                                  int n_chunk) {
-    constexpr int S = MMREC_BWD_W_STAGES;
-    __shared__ __attribute__((aligned(1024))) float Xr[S][BW_BK * BW_BF];     // X tiles [item][f], S-stage ring
-    __shared__ __attribute__((aligned(1024))) float Gq[S - 1][BW_BK * 64];    // dY tiles [item][o] as they arrive
-    __shared__ __attribute__((aligned(1024))) g_bf8 Asp[2][12 * 64];          // their split MFMA fragments [2 kstep + otile][part][lane]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ft = wave & 3, ks = wave >> 2;
-    const int f0 = blockIdx.x * BW_BF;
-    const int nb = blockIdx.y * n_chunk, ne = min(nb + n_chunk, n);
-    const int rows = ne - nb;
-    const i32x4 rx = raw_rsrc(X + (size_t)nb * F + f0, (unsigned)rows * (unsigned)F * 4u - (unsigned)f0 * 4u);
-    const i32x4 rg = raw_rsrc(dY + (size_t)nb * 64, (unsigned)rows * 256u);
-    int vx[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) vx[j] = (2 * (2 * wave + j) + (lane >> 5)) * F * 4 + (lane & 31) * 16;
-    const int vg = (4 * wave + (lane >> 4)) * 256 + (lane & 15) * 16;
-    auto issue = [&](int t, int gb, int xb) {      // the dY tile FIRST: it is wanted one step before its X tile
-        lds_dma16<false>(rg, lds_addr(&Gq[gb][wave * 256]), vg, t * BW_BK * 256);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) lds_dma16<NT>(rx, lds_addr(&Xr[xb][(2 * wave + j) * 256]), vx[j], t * BW_BK * F * 4);
-    };
-    const int i = lane & 31, h = lane >> 5;
-    const bool do_db = dbpart && blockIdx.x == 0 && tid < 64;
-    f32x16 acc0 = {0}, acc1 = {0};
-    float dbacc = 0.f;
-    // each dY element is split ONCE per workgroup: wave w owns half (w & 1) of fragment (kstep = w >> 2, otile = (w >> 1) & 1)
-    auto split_g = [&](int gb, int ab) {
-        const float* gq = Gq[gb];
-        if (do_db) {
-#pragma unroll
-            for (int k = 0; k < BW_BK; ++k) dbacc += gq[k * 64 + tid];
-        }
-        const int frag = wave >> 1, half = wave & 1;
-        const float* gr = gq + (16 * (frag >> 1) + 8 * h + 4 * half) * 64 + 32 * (frag & 1) + i;
-        g_bf4 a1, a2, a3;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float x = gr[e * 64];
-            const __bf16 b1 = (__bf16)x;
-            const float r1 = x - (float)b1;
-            const __bf16 b2 = (__bf16)r1;
-            a1[e] = b1;
-            a2[e] = b2;
-            a3[e] = (__bf16)(r1 - (float)b2);
-        }
-        g_bf4* dst = reinterpret_cast<g_bf4*>(&Asp[ab][frag * 3 * 64 + lane]) + half;
-        dst[0] = a1;
-        dst[128] = a2;
-        dst[256] = a3;
-    };
-    auto compute = [&](int ab, int xb) {
-        const float* xr = Xr[xb] + (16 * ks + 8 * h) * BW_BF + 32 * ft + i;
-        g_bf8 b1, b2, b3;
-        {
-            float xv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) xv[e] = xr[e * BW_BF];
-            split3(xv, b1, b2, b3);
-        }
-        {   // output tile 0 (o = i)
-            const g_bf8* ap = &Asp[ab][(2 * ks) * 3 * 64 + lane];
-            const g_bf8 a1 = ap[0], a2 = ap[64], a3 = ap[128];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc0, 0, 0, 0);
-        }
-        {   // output tile 1 (o = 32 + i)
-            const g_bf8* ap = &Asp[ab][(2 * ks + 1) * 3 * 64 + lane];
-            const g_bf8 a1 = ap[0], a2 = ap[64], a3 = ap[128];
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc1, 0, 0, 0);
-        }
-    };
-    // vmcnt queue: [G(0) X(0)] [G(1) X(1)] ... (1 + 2 copies per tile and wave), S - 1 tiles ahead, tiles past the end included
-    // (zero fill): step t wants X(t) and G(t + 1), i.e. at most X(t + 1) and the S - 3 groups behind it still in flight.
-    const int T = (rows + BW_BK - 1) / BW_BK;
-    if (T > 0) {
-#pragma unroll
-        for (int u = 0; u < S - 1; ++u) issue(u, u, u);
-        MMREC_WAIT_VM(2 + 3 * (S - 2));
-        __builtin_amdgcn_s_barrier();
-        split_g(0, 0);
-    }
-    int xb = 0, gb = 0;                                          // t % S, t % (S - 1)
-    for (int t = 0; t < T; ++t) {
-        MMREC_WAIT_VM(2 + 3 * (S - 3));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's part of tile t's fragments is in Asp
-        __builtin_amdgcn_s_barrier();
-        const int gn = gb == S - 2 ? 0 : gb + 1;
-        // (the two waves of a SIMD running these phases in opposite order -- one's MFMAs under the other's copies and splits --
-        // measured 2 us slower at Baby size, 10 us at Sports size: the later copies cost more than the overlap gives)
-        issue(t + S - 1, gb, xb == 0 ? S - 1 : xb - 1);
-        if (t + 1 < T) split_g(gn, (t + 1) & 1);
-        compute(t & 1, xb);
-        xb = xb == S - 1 ? 0 : xb + 1;
-        gb = gn;
-    }
-    MMREC_WAIT_VM(0);      // (the zero-fill copies of the tiles past the end)
-    if (do_db) dbpart[blockIdx.y * 64 + tid] = dbacc;
-    // the two k-step halves: waves 4-7 hand theirs over through LDS (the X ring is free now: 64 x 128 floats)
-    float* red = &Xr[0][0];
-    static_assert(S * BW_BK * BW_BF >= 64 * BW_BF, "the X ring holds the 64 x 128 hand-over tile");
-    __builtin_amdgcn_s_barrier();
-    if (ks == 1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = d_row(r, lane);
-            red[o * BW_BF + ft * 32 + i] = acc0[r];
-            red[(32 + o) * BW_BF + ft * 32 + i] = acc1[r];
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (ks == 0) {
-        float* dst = part + (size_t)blockIdx.y * 64 * F;
-        const int f = f0 + ft * 32 + i;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = d_row(r, lane);
-            dst[(size_t)o * F + f] = acc0[r] + red[o * BW_BF + ft * 32 + i];
-            dst[(size_t)(32 + o) * F + f] = acc1[r] + red[(32 + o) * BW_BF + ft * 32 + i];
-        }
-    }
-}
-
-// ---- Round 6: the same product with the dY side split ONCE PER CALL instead of once per workgroup ---------------------------
-// In the kernel above every one of the F / 128 column-block workgroups splits the same 32 x 64 dY tile again (a third of its VALU
-// work), through an LDS round trip (Gq -> registers -> Asp) that sits between the tile's barrier and its MFMAs, and the workgroups
-// with blockIdx.x == 0 also carry the bias gradient.  At 39 us for Amazon-Baby (X at 2.9 TB/s, MFMA pipe busy 30 %) nothing was
-// near a hardware limit: per 32-item tile a CU spent ~3,400 cycles where its MFMAs take 768 and its VALU work ~600 -- latency
-// chains between one barrier and the next, with a single 8-wave workgroup per CU to hide them.
-//   bwd_dy_split_kernel   dY -> the three bf16 parts of every tile, ALREADY in MFMA A-fragment layout (12 KB per 32-item tile,
-//                         [2 kstep + otile][part][lane] x 16 B: the old Asp image), + the bias gradient's partial sums;
-//   linear_bwd_w_v2       X tiles by LDS-DMA (3-stage ring) AND the ready-made A fragments by LDS-DMA (linear 12-KB copies: no
-//                         VALU, no LDS write, nothing between barrier and MFMAs but the X split); 72 KB of LDS, so TWO
-//                         workgroups share a CU and one's barrier wait runs under the other's MFMAs.
-// Same six products in the same order into the same accumulators as the kernel above: bit-identical dW; db's partial sums are
-// regrouped (per dy-split workgroup instead of per item chunk), fixed order, still free of atomics.
-#ifndef MMREC_BWD_W_V2
-#define MMREC_BWD_W_V2 1        // 0: the round-5 kernel (A/B: tools/prof_linear.py build-variants v1=-DMMREC_BWD_W_V2=0)
-#endif
-#ifndef MMREC_BWD_W2_AS
-#define MMREC_BWD_W2_AS 2       // A-fragment tiles in the LDS ring (2: issued one tile ahead; 3: two ahead, 84 KB = one workgroup per CU)
-#endif
-#ifndef MMREC_BWD_W2_OCC
-#define MMREC_BWD_W2_OCC 2      // workgroups per CU the kernel is compiled for (waves per SIMD = 2 x this)
-#endif
 constexpr int BW2_ATILE = 12 * 64 * 16;      // bytes of a tile's split dY fragments
 
-// grid: min(#tiles, 256) workgroups of 4 waves; workgroup g takes tiles g, g + G, ...; wave w = fragment (kstep = w >> 1, otile = w & 1).
+// grid: min(#tiles, 64) workgroups of 4 waves; workgroup g takes tiles g, g + G, ...; wave w = fragment (kstep = w >> 1, otile = w & 1).
 __device__ __forceinline__ void bwd_dy_split_body(int block, int n_blocks, const float* __restrict__ dY, int n,
                                                   g_bf8* __restrict__ Asp_g, float* __restrict__ dbpart) {
     __shared__ float s_db[4][64];
@@ -1041,25 +892,16 @@ __global__ __launch_bounds__(256) void bwd_w_finish_kernel(const float* __restri
     if (nslab <= 1) return;            // (a single chunk wrote dW itself)
     const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i4 * 4 >= slab_elems) return;
-    float4 t0 = f4_zero(), t1 = f4_zero(), t2 = f4_zero(), t3 = f4_zero();
-    int s = 0;
-    for (; s + 3 < nslab; s += 4) {      // four independent chains, fixed combination order (as slab_reduce_kernel)
-        t0 = f4_add(t0, reinterpret_cast<const float4*>(part + (size_t)(s + 0) * slab_elems)[i4]);
-        t1 = f4_add(t1, reinterpret_cast<const float4*>(part + (size_t)(s + 1) * slab_elems)[i4]);
-        t2 = f4_add(t2, reinterpret_cast<const float4*>(part + (size_t)(s + 2) * slab_elems)[i4]);
-        t3 = f4_add(t3, reinterpret_cast<const float4*>(part + (size_t)(s + 3) * slab_elems)[i4]);
-    }
-    for (; s < nslab; ++s) t0 = f4_add(t0, reinterpret_cast<const float4*>(part + (size_t)s * slab_elems)[i4]);
-    reinterpret_cast<float4*>(dW)[i4] = f4_add(f4_add(t0, t1), f4_add(t2, t3));
+    reinterpret_cast<float4*>(dW)[i4] = slab_sum4(part, nslab, slab_elems, i4);
 }
 
-template <bool NT, bool G = false>     // G: X is a table and item j of the contraction is X[ids[j]] (see "gathered operand rows")
-__global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_kernel(const g_bf8* __restrict__ Asp_g,
-                                                                                    const float* __restrict__ X,
-                                                                                    float* __restrict__ part, int n, int F, int n_chunk,
-                                                                                    const int64_t* __restrict__ ids = nullptr,
-                                                                                    int64_t n_table = 0) {
-    constexpr int S = 3, AS = MMREC_BWD_W2_AS;
+// NT: X does not fit the Infinity Cache and is read once per call: streamed non-temporal (as in the forward); G: X is a table and
+// item j of the contraction is X[ids[j]] (see "gathered operand rows").  Compiled for two workgroups per CU (4 waves per SIMD).
+template <bool NT, bool G = false>
+__global__ __launch_bounds__(512, 4) void linear_bwd_w_v2_kernel(const g_bf8* __restrict__ Asp_g, const float* __restrict__ X,
+                                                                 float* __restrict__ part, int n, int F, int n_chunk,
+                                                                 const int64_t* __restrict__ ids, int64_t n_table) {
+    constexpr int S = 3, AS = 2;      // X tiles / A-fragment tiles in the LDS rings (the A tiles are issued one tile ahead)
     __shared__ __attribute__((aligned(1024))) float Xr[S][BW_BK * BW_BF];      // X tiles [item][f], 3-stage ring (48 KB)
     __shared__ __attribute__((aligned(1024))) g_bf8 Ar[AS][12 * 64];           // split dY fragments of a tile (12 KB each)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1127,7 +969,7 @@ __global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_ker
         const g_bf8 a1 = ap[0], a2 = ap[64], a3 = ap[128], c1 = ap[192], c2 = ap[256], c3 = ap[320];
         g_bf8 b1, b2, b3;
         split3(xv, b1, b2, b3);
-        // smallest products first, exactly as in the round-5 kernel
+        // smallest products first
         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c3, b1, acc1, 0, 0, 0);
         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc0, 0, 0, 0);
@@ -1141,10 +983,9 @@ __global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_ker
         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, b1, acc1, 0, 0, 0);
     };
-    // vmcnt queue of a wave (AS = 2):  A(0) X(0) X(1) | A(1) X(2) | A(2) X(3) | ...   -- step t issues A(t + 1) BEFORE X(t + 2), so
-    // that "all but the two newest copies have landed" means X(t) and A(t) whatever a wave's number of A pieces.
-    // (AS = 3: A(0) A(1) X(0) X(1) | A(2) X(2) | ...: the newest 2 + nA copies may be in flight.)  Tiles past the end are issued
-    // too: out of the descriptors' range, they fill with zeros and are never multiplied.
+    // vmcnt queue of a wave:  A(0) X(0) X(1) | A(1) X(2) | A(2) X(3) | ...   -- step t issues A(t + 1) BEFORE X(t + 2), so that "all
+    // but the two newest copies have landed" means X(t) and A(t) whatever a wave's number of A pieces.  Tiles past the end are
+    // issued too: out of the descriptors' range, they fill with zeros and are never multiplied.
     if (T > 0) {
         if (G) {
             load_ids(0);
@@ -1152,18 +993,13 @@ __global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_ker
             load_ids(1);
         }
         issue_a(0);
-        if (AS == 3) issue_a(1);
         issue_x(0);
         issue_x(1);
     }
     for (int t = 0; t < T; ++t) {
-        if (AS == 3) {
-            if (wave < 4) MMREC_WAIT_VM(4); else MMREC_WAIT_VM(3);
-        } else {
-            MMREC_WAIT_VM(2);
-        }
+        MMREC_WAIT_VM(2);
         __builtin_amdgcn_s_barrier();       // everyone's pieces of tile t are in LDS; everyone has read tile t - 1
-        issue_a(t + AS - 1);
+        issue_a(t + 1);
         issue_x(t + 2);
         compute(t % AS, t % S);
     }
@@ -1199,7 +1035,9 @@ __global__ __launch_bounds__(512, 2 * MMREC_BWD_W2_OCC) void linear_bwd_w_v2_ker
 // split -- in registers for the whole walk and issue LDS reads, 12 MFMAs and 16 row-segment stores per 32-column sub-tile; wave 4
 // brings the pre-split W^T tiles (32 KB, linear) and their 128 column scales by LDS-DMA into a double buffer and is the only wave
 // that waits on vmcnt.  Output-write bound: n F 4 bytes.
-template <int STORE_AUX>     // cache policy bits of the dX stores (2 = nt: a dX larger than the Infinity Cache is written once and not re-read here)
+// STORE_AUX: cache policy bits of the dX stores.  Only 0, the default policy, is instantiated: non-temporal stores (2) of a dX larger
+// than the Infinity Cache measured 4 ... 12 % slower at 62,500 / 500,000 rows (profiles/r05_linear_bwd_nt_ab.log).
+template <int STORE_AUX>
 __global__ __launch_bounds__(320, 2) void bwd_x_f16x3_kernel(const float* __restrict__ dY, const float* __restrict__ Wt_sp,
                                                              const float* __restrict__ wcs_inv, float* __restrict__ dX, int n,
                                                              int F, int ftiles) {
@@ -1348,43 +1186,37 @@ inline void pick_split_stream(int tiles, int extent, int gran, int* nsplit, int*
     *nsplit = ceil_div(extent, *chunk);
 }
 
-}  // namespace
+// X (or the rows of it that are read) larger than this does not stay in the 256 MB Infinity Cache and is read once per call: it
+// is streamed non-temporally.  (Gathered: the same rule on the size of the rows that are READ, so that a row's k walk -- the NT
+// form of the split forward rotates it -- is the dense kernel's on the gathered copy.)
+inline bool streams_from_hbm(int n, int F) { return (size_t)n * F * sizeof(float) > ((size_t)192 << 20); }
 
-extern "C" size_t mmrec_linear_workspace_bytes(int32_t n, int32_t F, int32_t out) {
-    if (n <= 0 || F <= 0 || out <= 0 || (out & 63)) return 0;   // out > 64: only the dW call uses it
-    int s1, c1, s2, c2, s1s, c1s;
-    pick_split(ceil_div(n, LIN_BM), F, LIN_BK, &s1, &c1);
-    pick_split_stream(ceil_div(n, LIN_BM), F, LIN_BK, &s1s, &c1s);      // (the split-operand forward's rule)
-    if (s1s > s1) s1 = s1s;
-#ifdef MMREC_FWD_SPLIT      // probe builds force the forward's split count: room for their slabs
-    if (s1 < MMREC_FWD_SPLIT + 1) s1 = MMREC_FWD_SPLIT + 1;
-#endif
-    pick_split(ceil_div(F, BW_BF), n, BW_BK, &s2, &c2);
-    // forward: partial slabs, then (mmrec_linear_fwd_split_f32) the 64 x F split copy of W, the per-slab row maxima of |X| and
-    // the redo flags of its domain check (one per 128-row block + one per W row)
-    const size_t fwd = ((s1 > 1 ? (size_t)s1 * n * 64 * sizeof(float) : 0) + 255) / 256 * 256 + (size_t)64 * F * sizeof(float) +
-                       (s1 > 1 ? (size_t)s1 * n * sizeof(float) : 0) + ((size_t)ceil_div(n, LIN_BM) + 64) * sizeof(int);
-    const size_t bww = ((s2 > 1 ? (size_t)s2 * 64 * F : 0) + (size_t)s2 * 64) * sizeof(float) * (size_t)(out / 64);   // every 64-output group its own slabs
-    return fwd > bww ? fwd : bww;
-}
-
-namespace {
 // a gathered X operand: rows T[ids[j]] of a table with n_table rows (ids == nullptr: X itself, consecutive rows)
 struct RowList {
     const int64_t* ids;
     int64_t n_table;
 };
-int linear_fwd_f32_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
-                        void* workspace, mmrec_stream_t stream);
-}  // namespace
-
-extern "C" int mmrec_linear_fwd_f32(const float* X, const float* W, const float* b, float* Y,
-                                    int32_t n, int32_t F, int32_t out, void* workspace,
-                                    mmrec_stream_t stream) {
-    return linear_fwd_f32_impl(X, RowList{nullptr, 0}, W, b, Y, n, F, out, workspace, stream);
+// The one place where (nt, gathered) become the template arguments <NT, G> of a kernel: launch(nt_c, g_c) gets them as two
+// std::bool_constant values.
+template <class Launch>
+inline void with_nt_g(bool nt, bool gathered, Launch launch) {
+    if (gathered) {
+        if (nt) launch(std::true_type{}, std::true_type{});
+        else launch(std::false_type{}, std::true_type{});
+    } else {
+        if (nt) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
+}
+// linear_fwd_dma_kernel over `grid` (redo: the fix-up launch of the split forward, else nullptr)
+inline void launch_fwd_dma(dim3 grid, hipStream_t s, const float* X, RowList g, const float* W, const float* b, float* dst, int n, int F,
+                           int chunk, const int* redo) {
+    with_nt_g(streams_from_hbm(n, F), g.ids != nullptr, [&](auto nt_c, auto g_c) {
+        hipLaunchKernelGGL((linear_fwd_dma_kernel<decltype(nt_c)::value, decltype(g_c)::value>), grid, dim3(256), 0, s, X, W, b, dst, n, F,
+                           chunk, redo, g.ids, g.n_table);
+    });
 }
 
-namespace {
 int linear_fwd_f32_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
                         void* workspace, mmrec_stream_t stream) {
     if (out != 64 || F <= 0 || (F & 3)) return MMREC_ERR_UNSUPPORTED;
@@ -1393,53 +1225,25 @@ int linear_fwd_f32_impl(const float* X, RowList g, const float* W, const float* 
     if (!X || !W || !Y) return MMREC_ERR_BAD_ARG;
     int nsplit, chunk;
     pick_split(ceil_div(n, LIN_BM), F, LIN_BK, &nsplit, &chunk);
-#ifdef MMREC_FWD_SPLIT
-    chunk = ceil_div(ceil_div(F, MMREC_FWD_SPLIT), LIN_BK) * LIN_BK; nsplit = ceil_div(F, chunk);
-#endif
     hipStream_t s = mmrec_stream(stream);
-    const bool dma = (F % DM_BK) == 0 && !MMREC_GEMM_LEGACY_FWD;
     if (nsplit > 1 && !workspace) return MMREC_ERR_BAD_ARG;
     float* dst = nsplit == 1 ? Y : static_cast<float*>(workspace);
     const dim3 grid(ceil_div(n, LIN_BM), nsplit);
-    // X larger than the 256 MB Infinity Cache is read once per call: stream it non-temporal
-    const bool nt = (size_t)n * F * sizeof(float) > ((size_t)192 << 20);
-    if (g.ids) {      // (mmrec_linear_rows_fwd_f32 has checked F % 128 == 0: always the LDS-DMA kernel)
-        if (nt)
-            hipLaunchKernelGGL((linear_fwd_dma_kernel<true, true>), grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr,
-                               g.ids, g.n_table);
-        else
-            hipLaunchKernelGGL((linear_fwd_dma_kernel<false, true>), grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr,
-                               g.ids, g.n_table);
-    } else if (dma && nt)
-        hipLaunchKernelGGL(linear_fwd_dma_kernel<true>, grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr);
-    else if (dma)
-        hipLaunchKernelGGL(linear_fwd_dma_kernel<false>, grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk, (const int*)nullptr);
-    else
-        hipLaunchKernelGGL(linear_fwd_kernel<MMREC_GEMM_PROBE_MODE>, grid, dim3(256),
-                           MMREC_GEMM_DYN_LDS, s, X, W, b, dst, n, F, chunk);
+    // (gathered: mmrec_linear_rows_fwd_f32 has checked F % 128 == 0: always the LDS-DMA kernel)
+    if ((F % DM_BK) == 0) launch_fwd_dma(grid, s, X, g, W, b, dst, n, F, chunk, nullptr);
+    else hipLaunchKernelGGL(linear_fwd_kernel<0>, grid, dim3(256), 0, s, X, W, b, dst, n, F, chunk);
     if (nsplit > 1) {
-        float* part = dst;
         const size_t elems = (size_t)n * 64;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0,
-                           s, part, nsplit, elems, b, Y);
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0, s, (const float*)dst, nsplit,
+                           elems, b, Y, (const float*)nullptr, (int*)nullptr);
     }
     MMREC_RETURN_LAUNCH_STATUS();
 }
-}  // namespace
 
 // mmrec_linear_fwd_f32 on the 16-bit matrix cores with split operands (fp32-accurate: see linear_fwd_dma_f16x3_kernel).  F % 32 != 0
 // takes the fp32 kernels.  Rows / weights outside the split's domain (|.| >= 65520, inf, NaN, or a whole row below 2^-10) are
 // detected on the device and recomputed by the fp32 kernel in the same call (no host synchronisation): see the kernel's comment.
 // Workspace: mmrec_linear_workspace_bytes (slabs | split W | per-slab row maxima | redo flags).
-namespace {
-int linear_fwd_split_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
-                          void* workspace, mmrec_stream_t stream);
-}  // namespace
-extern "C" int mmrec_linear_fwd_split_f32(const float* X, const float* W, const float* b, float* Y, int32_t n, int32_t F,
-                                          int32_t out, void* workspace, mmrec_stream_t stream) {
-    return linear_fwd_split_impl(X, RowList{nullptr, 0}, W, b, Y, n, F, out, workspace, stream);
-}
-namespace {
 int linear_fwd_split_impl(const float* X, RowList g, const float* W, const float* b, float* Y, int32_t n, int32_t F, int32_t out,
                           void* workspace, mmrec_stream_t stream) {
     if (out != 64 || F <= 0 || (F & 3)) return MMREC_ERR_UNSUPPORTED;
@@ -1449,9 +1253,6 @@ int linear_fwd_split_impl(const float* X, RowList g, const float* W, const float
     if (!X || !W || !Y || !workspace) return MMREC_ERR_BAD_ARG;
     int nsplit, chunk;
     pick_split_stream(ceil_div(n, LIN_BM), F, LIN_BK, &nsplit, &chunk);
-#ifdef MMREC_FWD_SPLIT      // probe (tools/prof_linear_replay.py ab): force the split-K count
-    chunk = ceil_div(ceil_div(F, MMREC_FWD_SPLIT), LIN_BK) * LIN_BK; nsplit = ceil_div(F, chunk);
-#endif
     hipStream_t s = mmrec_stream(stream);
     const int nblocks = ceil_div(n, LIN_BM);
     float* part = static_cast<float*>(workspace);
@@ -1461,44 +1262,24 @@ int linear_fwd_split_impl(const float* X, RowList g, const float* W, const float
     int* redo = reinterpret_cast<int*>(rowmax_part + (nsplit > 1 ? (size_t)nsplit * n : 0));
     hipLaunchKernelGGL(linear_w_split_kernel, dim3(64), dim3(256), 0, s, W, F, Wsp, redo, nblocks);
     float* dst = nsplit == 1 ? Y : part;
-    const dim3 grid(nblocks, nsplit);
-    // (gathered: the same rule on the size of the rows that are READ, so that a row's k walk -- the NT form rotates it -- is the
-    // dense kernel's on the gathered copy)
-    const bool nt = (size_t)n * F * sizeof(float) > ((size_t)192 << 20);
-    if (g.ids && nt)
-        hipLaunchKernelGGL((linear_fwd_dma_f16x3_kernel<true, true>), grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo,
-                           g.ids, g.n_table);
-    else if (g.ids)
-        hipLaunchKernelGGL((linear_fwd_dma_f16x3_kernel<false, true>), grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo,
-                           g.ids, g.n_table);
-    else if (nt)
-        hipLaunchKernelGGL(linear_fwd_dma_f16x3_kernel<true>, grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo);
-    else
-        hipLaunchKernelGGL(linear_fwd_dma_f16x3_kernel<false>, grid, dim3(256), 0, s, X, Wsp, b, dst, n, F, chunk, rowmax_part, redo);
+    with_nt_g(streams_from_hbm(n, F), g.ids != nullptr, [&](auto nt_c, auto g_c) {
+        hipLaunchKernelGGL((linear_fwd_dma_f16x3_kernel<decltype(nt_c)::value, decltype(g_c)::value>), dim3(nblocks, nsplit), dim3(256), 0,
+                           s, X, (const float*)Wsp, b, dst, n, F, chunk, rowmax_part, redo, g.ids, g.n_table);
+    });
     if (nsplit > 1) {
         const size_t elems = (size_t)n * 64;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0, s, part, nsplit, elems,
-                           b, Y, (const float*)rowmax_part, redo);
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0, s, (const float*)part, nsplit,
+                           elems, b, Y, (const float*)rowmax_part, redo);
     }
     // fix-up: the fp32 kernel over the flagged 128-row blocks (the others return at once), whole K per workgroup
-    if (g.ids && nt)
-        hipLaunchKernelGGL((linear_fwd_dma_kernel<true, true>), dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo,
-                           g.ids, g.n_table);
-    else if (g.ids)
-        hipLaunchKernelGGL((linear_fwd_dma_kernel<false, true>), dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo,
-                           g.ids, g.n_table);
-    else if (nt)
-        hipLaunchKernelGGL(linear_fwd_dma_kernel<true>, dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo);
-    else
-        hipLaunchKernelGGL(linear_fwd_dma_kernel<false>, dim3(nblocks, 1), dim3(256), 0, s, X, W, b, Y, n, F, F, (const int*)redo);
+    launch_fwd_dma(dim3(nblocks, 1), s, X, g, W, b, Y, n, F, F, redo);
     MMREC_RETURN_LAUNCH_STATUS();
 }
-}  // namespace
 
 // ---- ABI 11: the projection's backward on the 16-bit matrix cores (see the kernels' comment block) ----------------------------
 // Workspace layout (mmrec_linear_bwd_split_workspace_bytes): [W^T split: F x 256 B][wcs_inv: F + 256 floats][db partials:
-// nsplit x 64 floats][dW slabs: nsplit > 1 ? nsplit x 64 x F floats]; never smaller than what the fp32 entry points need.
-namespace {
+// max(nsplit, dy_wgs) x 64 floats][dW slabs: nsplit > 1 ? nsplit x 64 x F floats][dY split: 384 B per item]; never smaller than
+// what the fp32 entry points need.
 struct BwdSplitWs {
     size_t wt, wcs, dbp, slabs, asp, total;
     int nsplit, chunk, dy_wgs;
@@ -1507,11 +1288,8 @@ inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 inline BwdSplitWs bwd_split_ws(int n, int F) {
     BwdSplitWs w;
     pick_split_stream(ceil_div(F, BW_BF), n, BW_BK, &w.nsplit, &w.chunk);
-    // (the v2 kernel fits two workgroups per CU, but twice the chunks measured 3 % SLOWER forward + backward at 7,050 rows and the
+    // (the dW kernel fits two workgroups per CU, but twice the chunks measured 3 % SLOWER forward + backward at 7,050 rows and the
     // same at 18,357 -- twice the slabs to sum; a quarter of the chunks 10 % slower: profiles/r06_linear_bwd_w_v2_ab.log)
-#ifdef MMREC_BWD_W_SPLIT    // probe: force the split-over-items count of the dW kernel
-    w.chunk = ceil_div(ceil_div(n, MMREC_BWD_W_SPLIT), BW_BK) * BW_BK; w.nsplit = ceil_div(n, w.chunk);
-#endif
     // LDS-DMA scalar offsets of the dW kernel: a workgroup's item chunk must stay below 2^31 bytes of X
     while ((size_t)(w.chunk + 8 * BW_BK) * F * 4 >= ((size_t)1 << 31)) {      // (+ the tiles issued past the end)
         w.chunk = ceil_div(w.chunk / 2, BW_BK) * BW_BK;
@@ -1526,37 +1304,19 @@ inline BwdSplitWs bwd_split_ws(int n, int F) {
     w.dy_wgs = n_tiles < 64 ? n_tiles : 64;
     w.dbp = off; off += al256((size_t)(w.nsplit > w.dy_wgs ? w.nsplit : w.dy_wgs) * 64 * 4);
     w.slabs = off; off += al256(w.nsplit > 1 ? (size_t)w.nsplit * 64 * F * 4 : 0);
-    w.asp = off; off += MMREC_BWD_W_V2 ? al256((size_t)n_tiles * BW2_ATILE) : 0;      // dY split once per call: 384 B per item
+    w.asp = off; off += al256((size_t)n_tiles * BW2_ATILE);      // dY split once per call: 384 B per item
     w.total = off;
     return w;
 }
-#ifndef MMREC_BWD_NT
-#define MMREC_BWD_NT 1     // bit 0 = dW reads an X larger than the Infinity Cache non-temporal (measured: -14 % forward + backward at Sports / Clothing size), bit 1 = dX written non-temporal (measured: +4 ... +12 % at 62,500 / 500,000 rows: off); profiles/r05_linear_bwd_nt_ab.log, tools/prof_linear.py run-variants
-#endif
-constexpr bool BWD_X_NT_STORES = (MMREC_BWD_NT & 2) != 0;
 inline bool bwd_split_serves(int n, int F, int out) { return out == 64 && n > 0 && F > 0 && (F % BW_BF) == 0; }
-}  // namespace
-
-extern "C" size_t mmrec_linear_bwd_split_workspace_bytes(int32_t n, int32_t F, int32_t out) {
-    const size_t plain = mmrec_linear_workspace_bytes(n, F, out);
-    if (!bwd_split_serves(n, F, out)) return plain;
-    const size_t mine = bwd_split_ws(n, F).total;
-    return mine > plain ? mine : plain;
-}
+inline bool rows_serves(int F, int out) { return out == 64 && F > 0 && (F % BW_BF) == 0; }
 
 // dW [64, F] = dY^T X, db [64] = column sums of dY, dX [n, F] = dY W in ONE call (any of dW+db / dX may be NULL: not wanted).
 // out == 64 and F % 128 == 0 run the split-operand kernels; other shapes are handed to mmrec_linear_bwd_w_f32 /
 // mmrec_linear_bwd_x_f32 (same workspace).  Results: fp32-accurate (dW: error <= 2^-22 of sum |a b| per output + fp32
 // accumulation, any magnitudes; dX: 2^-21 with the operands scaled into fp16's range by exact powers of two).
-namespace {
-int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const float* W, float* dW, float* db, float* dX,
-                          int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream);
-}  // namespace
-extern "C" int mmrec_linear_bwd_split_f32(const float* dY, const float* X, const float* W, float* dW, float* db, float* dX,
-                                          int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream) {
-    return linear_bwd_split_impl(dY, X, RowList{nullptr, 0}, W, dW, db, dX, n, F, out, workspace, stream);
-}
-namespace {
+// dW reads an X larger than the Infinity Cache non-temporally (-14 % forward + backward at Sports / Clothing size); dX is stored
+// with the default policy (profiles/r05_linear_bwd_nt_ab.log).
 // (g.ids: only from mmrec_linear_rows_bwd_f32, which has checked that the split kernels serve the shape)
 int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const float* W, float* dW, float* db, float* dX,
                           int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream) {
@@ -1577,21 +1337,10 @@ int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const floa
     float* wcs_inv = reinterpret_cast<float*>(base + w.wcs);
     float* dbp = reinterpret_cast<float*>(base + w.dbp);
     float* slabs = reinterpret_cast<float*>(base + w.slabs);
-    const int ncb = F / BW_BF;
-    const bool big = (size_t)n * F * sizeof(float) > ((size_t)192 << 20);      // X / dX larger than the Infinity Cache
     bool wt_done = false;
-#ifdef MMREC_BWD_W_FP32      // probe: dW by the fp32-MFMA kernel inside the split entry (A/B against the bf16 x 3 kernel)
-    if (dW) {
-        const int rc = mmrec_linear_bwd_w_f32(dY, X, dW, db, n, F, out, workspace, stream);
-        if (rc) return rc;
-        dW = nullptr;
-    }
-#endif
     if (dW) {
         float* part = w.nsplit == 1 ? dW : slabs;
         float* dbpart = db ? dbp : (float*)nullptr;
-        int n_dbpart = w.nsplit;
-#if MMREC_BWD_W_V2
         g_bf8* Asp_g = reinterpret_cast<g_bf8*>(base + w.asp);
         if (dX) {       // dY and W^T are split in one launch
             hipLaunchKernelGGL(bwd_prep_kernel, dim3(w.dy_wgs + ceil_div(F, 256)), dim3(256), 0, s, dY, n, Asp_g, dbpart, w.dy_wgs,
@@ -1600,27 +1349,14 @@ int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const floa
         } else {
             hipLaunchKernelGGL(bwd_dy_split_kernel, dim3(w.dy_wgs), dim3(256), 0, s, dY, n, Asp_g, dbpart);
         }
-        n_dbpart = w.dy_wgs;
-        if (g.ids && big && (MMREC_BWD_NT & 1))
-            hipLaunchKernelGGL((linear_bwd_w_v2_kernel<true, true>), dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F,
-                               w.chunk, g.ids, g.n_table);
-        else if (g.ids)
-            hipLaunchKernelGGL((linear_bwd_w_v2_kernel<false, true>), dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F,
-                               w.chunk, g.ids, g.n_table);
-        else if (big && (MMREC_BWD_NT & 1))
-            hipLaunchKernelGGL(linear_bwd_w_v2_kernel<true>, dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F, w.chunk);
-        else
-            hipLaunchKernelGGL(linear_bwd_w_v2_kernel<false>, dim3(ncb, w.nsplit), dim3(512), 0, s, (const g_bf8*)Asp_g, X, part, n, F, w.chunk);
-#else
-        if (big && (MMREC_BWD_NT & 1))
-            hipLaunchKernelGGL(linear_bwd_w_bf16x3_kernel<true>, dim3(ncb, w.nsplit), dim3(512), 0, s, dY, X, part, dbpart, n, F, w.chunk);
-        else
-            hipLaunchKernelGGL(linear_bwd_w_bf16x3_kernel<false>, dim3(ncb, w.nsplit), dim3(512), 0, s, dY, X, part, dbpart, n, F, w.chunk);
-#endif
+        with_nt_g(streams_from_hbm(n, F), g.ids != nullptr, [&](auto nt_c, auto g_c) {
+            hipLaunchKernelGGL((linear_bwd_w_v2_kernel<decltype(nt_c)::value, decltype(g_c)::value>), dim3(F / BW_BF, w.nsplit), dim3(512),
+                               0, s, (const g_bf8*)Asp_g, X, part, n, F, w.chunk, g.ids, g.n_table);
+        });
         if (w.nsplit > 1 || db) {      // slabs -> dW and partials -> db, one launch
             const size_t elems = (size_t)64 * F;
             hipLaunchKernelGGL(bwd_w_finish_kernel, dim3((unsigned)((elems / 4 + 255) / 256) + 1), dim3(256), 0, s, (const float*)slabs,
-                               w.nsplit, elems, dW, (const float*)dbp, n_dbpart, db);
+                               w.nsplit, elems, dW, (const float*)dbp, w.dy_wgs, db);
         }
     }
     if (dX) {
@@ -1628,17 +1364,51 @@ int linear_bwd_split_impl(const float* dY, const float* X, RowList g, const floa
         const int rt = ceil_div(n, 128), nft = F / 128;
         int ftiles = 8;
         while (ftiles > 1 && (long)rt * ceil_div(nft, ftiles) < 192) ftiles >>= 1;
-        if (big && BWD_X_NT_STORES)
-            hipLaunchKernelGGL(bwd_x_f16x3_kernel<2>, dim3(rt, ceil_div(nft, ftiles)), dim3(320), 0, s, dY, (const float*)Wt_sp,
-                               (const float*)wcs_inv, dX, n, F, ftiles);
-        else
-            hipLaunchKernelGGL(bwd_x_f16x3_kernel<0>, dim3(rt, ceil_div(nft, ftiles)), dim3(320), 0, s, dY, (const float*)Wt_sp,
-                               (const float*)wcs_inv, dX, n, F, ftiles);
+        hipLaunchKernelGGL(bwd_x_f16x3_kernel<0>, dim3(rt, ceil_div(nft, ftiles)), dim3(320), 0, s, dY, (const float*)Wt_sp,
+                           (const float*)wcs_inv, dX, n, F, ftiles);
     }
     MMREC_RETURN_LAUNCH_STATUS();
 }
-inline bool rows_serves(int F, int out) { return out == 64 && F > 0 && (F % BW_BF) == 0; }
+
 }  // namespace
+
+extern "C" size_t mmrec_linear_workspace_bytes(int32_t n, int32_t F, int32_t out) {
+    if (n <= 0 || F <= 0 || out <= 0 || (out & 63)) return 0;   // out > 64: only the dW call uses it
+    int s1, c1, s2, c2, s1s, c1s;
+    pick_split(ceil_div(n, LIN_BM), F, LIN_BK, &s1, &c1);
+    pick_split_stream(ceil_div(n, LIN_BM), F, LIN_BK, &s1s, &c1s);      // (the split-operand forward's rule)
+    if (s1s > s1) s1 = s1s;
+    pick_split(ceil_div(F, BW_BF), n, BW_BK, &s2, &c2);
+    // forward: partial slabs, then (mmrec_linear_fwd_split_f32) the 64 x F split copy of W, the per-slab row maxima of |X| and
+    // the redo flags of its domain check (one per 128-row block + one per W row)
+    const size_t fwd = ((s1 > 1 ? (size_t)s1 * n * 64 * sizeof(float) : 0) + 255) / 256 * 256 + (size_t)64 * F * sizeof(float) +
+                       (s1 > 1 ? (size_t)s1 * n * sizeof(float) : 0) + ((size_t)ceil_div(n, LIN_BM) + 64) * sizeof(int);
+    const size_t bww = ((s2 > 1 ? (size_t)s2 * 64 * F : 0) + (size_t)s2 * 64) * sizeof(float) * (size_t)(out / 64);   // every 64-output group its own slabs
+    return fwd > bww ? fwd : bww;
+}
+
+extern "C" int mmrec_linear_fwd_f32(const float* X, const float* W, const float* b, float* Y,
+                                    int32_t n, int32_t F, int32_t out, void* workspace,
+                                    mmrec_stream_t stream) {
+    return linear_fwd_f32_impl(X, RowList{nullptr, 0}, W, b, Y, n, F, out, workspace, stream);
+}
+
+extern "C" int mmrec_linear_fwd_split_f32(const float* X, const float* W, const float* b, float* Y, int32_t n, int32_t F,
+                                          int32_t out, void* workspace, mmrec_stream_t stream) {
+    return linear_fwd_split_impl(X, RowList{nullptr, 0}, W, b, Y, n, F, out, workspace, stream);
+}
+
+extern "C" size_t mmrec_linear_bwd_split_workspace_bytes(int32_t n, int32_t F, int32_t out) {
+    const size_t plain = mmrec_linear_workspace_bytes(n, F, out);
+    if (!bwd_split_serves(n, F, out)) return plain;
+    const size_t mine = bwd_split_ws(n, F).total;
+    return mine > plain ? mine : plain;
+}
+
+extern "C" int mmrec_linear_bwd_split_f32(const float* dY, const float* X, const float* W, float* dW, float* db, float* dX,
+                                          int32_t n, int32_t F, int32_t out, void* workspace, mmrec_stream_t stream) {
+    return linear_bwd_split_impl(dY, X, RowList{nullptr, 0}, W, dW, db, dX, n, F, out, workspace, stream);
+}
 
 // ---- ABI 15: the projection of LISTED rows of a table, Y[j] = T[ids[j]] W^T + b, without the [n, F] copy of the rows --------
 // The same kernels, split plans and launches as mmrec_linear_fwd_f32 / mmrec_linear_fwd_split_f32 / mmrec_linear_bwd_split_f32
@@ -1665,9 +1435,6 @@ extern "C" int mmrec_linear_rows_bwd_f32(const float* dY, const float* T, int64_
                                          float* dW, float* db, float* dX, int32_t n, int32_t F, int32_t out, void* workspace,
                                          mmrec_stream_t stream) {
     if (!rows_serves(F, out)) return MMREC_ERR_UNSUPPORTED;
-#if !MMREC_BWD_W_V2 || defined(MMREC_BWD_W_FP32)      // (probe builds with another dW kernel: no gathered form)
-    return MMREC_ERR_UNSUPPORTED;
-#endif
     if (n < 0 || n_table < 0) return MMREC_ERR_BAD_ARG;
     if ((dW && (!T || !ids)) || (dX && !W) || (db && !dW)) return MMREC_ERR_BAD_ARG;
     if (n == 0) {       // an empty list: dW = 0, db = 0, nothing to write into dX
@@ -1706,8 +1473,7 @@ extern "C" int mmrec_linear_bwd_w_f32(const float* dY, const float* X, float* dW
     const int nz = out / 64;
     const size_t slab_z = nsplit > 1 ? (size_t)nsplit * 64 * F : 0;
     float* dbpart = db ? part + slab_z * nz : nullptr;
-    const bool dma = (size_t)chunk * F * 4 < ((size_t)1 << 31) && (size_t)chunk * out * 4 < ((size_t)1 << 31) &&
-                     !MMREC_GEMM_LEGACY_FWD;
+    const bool dma = (size_t)chunk * F * 4 < ((size_t)1 << 31) && (size_t)chunk * out * 4 < ((size_t)1 << 31);     // (scalar byte offsets)
     auto kern = dma ? linear_bwd_w_dma_kernel : linear_bwd_w_kernel;
     if (nsplit == 1) {
         hipLaunchKernelGGL(kern, dim3(ceil_div(F, BW_BF), 1, nz), dim3(256), 0, s, dY, X, dW, dbpart, n, F, chunk, out,
@@ -1717,7 +1483,7 @@ extern "C" int mmrec_linear_bwd_w_f32(const float* dY, const float* X, float* dW
                            (size_t)nsplit * 64);
         const size_t elems = (size_t)64 * F;
         hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256), nz), dim3(256), 0,
-                           s, part, nsplit, elems, (const float*)nullptr, dW);
+                           s, (const float*)part, nsplit, elems, (const float*)nullptr, dW, (const float*)nullptr, (int*)nullptr);
     }
     if (db) hipLaunchKernelGGL(db_reduce_kernel, dim3(nz), dim3(1024), 0, s, dbpart, nsplit, db);
     MMREC_RETURN_LAUNCH_STATUS();
@@ -1741,7 +1507,7 @@ extern "C" int mmrec_linear_bwd_x_f32(const float* dY, const float* W, float* dX
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     if (!dY || !W || !dX) return MMREC_ERR_BAD_ARG;
-    if (F % 128 == 0 && !MMREC_GEMM_LEGACY_FWD) {
+    if (F % 128 == 0) {
         gemm64_stream_launch(dY, W, dX, n, F, mmrec_stream(stream));
     } else {
         hipLaunchKernelGGL(linear_bwd_x_kernel, dim3(ceil_div(n, 128), ceil_div(F, 128)), dim3(256), 0,

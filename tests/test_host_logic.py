@@ -643,7 +643,7 @@ def _bf16_round(a):
 
 
 def test_bf16_three_way_split_projection_gradient_claim():
-    """gemm.hip linear_bwd_w_bf16x3_kernel, restated in numpy: x = b1 + b2 + b3 with b1 = bf16(x), b2 = bf16(x - b1),
+    """gemm.hip linear_bwd_w_v2_kernel (fed by bwd_dy_split_kernel), restated in numpy: x = b1 + b2 + b3 with b1 = bf16(x), b2 = bf16(x - b1),
     b3 = bf16(x - b1 - b2); dW = sum over items of the six products b_i c_j with i + j <= 4 (the three dropped ones are
     <= 2^-23 |x y|).  Claims checked: (1) the three parts restore x to 2^-24 relative -- for magnitudes 1e-30 ... 1e30 alike,
     no scale involved; (2) dW's error against float64 is <= 2^-22 sum |dy x| per output on a gradient column that spans 2^44

@@ -154,3 +154,40 @@ def test_tile_and_sweep_plans(lib):
     # 16 own tiles, target 512: 32 splits of the 111 tiles, 4 tiles each -- the same plan in both ops
     assert lib.mmrec_score_lse_split_cols(2048, 7050, 0) == 256
     assert lib.mmrec_tri_topk_split_cols(2048, 7050) == 256
+
+
+def test_projection_workspace_plans(lib):
+    """The workspace exports of the modal projection (gemm.hip), which launch nothing: the split plans and the layouts behind them
+    pinned to literals.  Notation: blocks = ceil(n / 128) row blocks; the fp32 plan `pick_split` minimises max(ceil(tiles s / 256),
+    2) x (chunk + 128 if s > 1) over at most 64 splits, the streaming plan `pick_split_stream` wants 256 / tiles splits (three
+    for 129 ... 170 tiles, one above) of at least two ring tiles each; al256 rounds up to a multiple of 256 bytes."""
+    ws, bs, rows = lib.mmrec_linear_workspace_bytes, lib.mmrec_linear_bwd_split_workspace_bytes, lib.mmrec_linear_rows_workspace_bytes
+    assert ws(0, 4096, 64) == 0 and ws(128, 4096, 100) == 0 and rows(0, 128, 64) == 0
+    # one block, one chunk: no slabs; split W 64 x 20 x 4 = 5,120 + redo flags (1 block + 64 W rows) x 4 = 260
+    assert ws(1, 20, 64) == 5120 + 260 == 5380
+    # 32 blocks: the fp32 forward splits K 16 ways (2 x (256 + 128) = 768 is its cheapest), the streaming one 8: slabs 16 x 4096 x
+    # 64 x 4 = 16,777,216 + split W 1,048,576 + row maxima 16 x 4096 x 4 = 262,144 + flags (32 + 64) x 4 = 384
+    assert ws(4096, 4096, 64) == 16777216 + 1048576 + 262144 + 384 == 18088320
+    # 180 blocks: 4 chunks of 1024 (3 rounds x 1152 = 3,456), the streaming plan 1: slabs 4 x 23,033 x 256 = 23,585,792 + split W
+    # 1,048,576 + row maxima 4 x 23,033 x 4 = 368,528 + flags (180 + 64) x 4 = 976
+    assert ws(23033, 4096, 64) == 23585792 + 1048576 + 368528 + 976 == 25003872
+    # out = 384, 2 blocks: the forward's 64 chunks of 64 outweigh dW's six groups of one chunk (6 x 64 x 4 = 1,536): slabs 64 x
+    # 129 x 256 = 2,113,536 + split W 1,048,576 + row maxima 64 x 129 x 4 = 33,024 + flags (2 + 64) x 4 = 264
+    assert ws(129, 4096, 384) == 2113536 + 1048576 + 33024 + 264 == 3195400
+    # one column block, 32,769 items: dW asks for 64 chunks of ceil(513 / 32) x 32 = 544 items, which makes 61; per 64-output group
+    # 61 slabs of 64 x 128 floats + 61 x 64 db partials = 503,616 floats; the forward (257 blocks, one chunk) needs 34,052 bytes
+    assert ws(32769, 128, 128) == 503616 * 4 * 2 == 4028928
+    assert ws(32769, 128, 384) == 503616 * 4 * 6 == 12086784
+    # backward split, larger than the fp32 calls' 33,032: 3 chunks of 64 items, 5 tiles of 32: W^T 128 x 256 = 32,768 + column
+    # scales (128 + 256) x 4 = 1,536 + db partials max(3, 5) x 256 = 1,280 + slabs 3 x 64 x 128 x 4 = 98,304 + dY split 5 x 12,288
+    assert ws(129, 128, 64) == 33032
+    assert bs(129, 128, 64) == 32768 + 1536 + 1280 + 98304 + 61440 == 195328
+    # 32 column blocks: 8 chunks of ceil(7813 / 32) x 32 = 7,840 items, 1,954 tiles, 64 dY-split workgroups: W^T 1,048,576 + scales
+    # al256(4,352 x 4) = 17,408 + db partials 64 x 256 = 16,384 + slabs 8 x 64 x 4096 x 4 = 8,388,608 + dY split 1,954 x 12,288
+    assert bs(62500, 4096, 64) == 1048576 + 17408 + 16384 + 8388608 + 24010752 == 33481728
+    # 3 column blocks, 128 items: 2 chunks of 64, 4 tiles: 98,304 + 2,560 + 1,024 + 2 x 64 x 384 x 4 = 196,608 + 4 x 12,288
+    assert bs(128, 384, 64) == 98304 + 2560 + 1024 + 196608 + 49152 == 347648
+    assert bs(129, 4096, 384) == ws(129, 4096, 384)            # out > 64: the fp32 calls serve it, and their workspace
+    # gathered rows: the backward split's size where it serves the shape (out = 64, F % 128 == 0), else 0
+    assert rows(128, 384, 64) == 347648 and rows(62500, 4096, 64) == 33481728
+    assert rows(7050, 96, 64) == 0 and rows(7050, 4096, 128) == 0

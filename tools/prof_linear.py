@@ -59,14 +59,13 @@ def main():
         del X, W, b, G, Xg
 
 
-VARIANTS = {"nt0": "-DMMREC_BWD_NT=0", "nt1_dw_reads": "-DMMREC_BWD_NT=1", "nt2_dx_stores": "-DMMREC_BWD_NT=2",
-            "nt3_both": "-DMMREC_BWD_NT=3"}          # builds of gemm.hip with extra flags
-
-
-def build_variants(specs=()):
-    """python tools/prof_linear.py build-variants [name=-DFLAG[,-DFLAG] ...]   (here, no GPU): tools/probe_libs/libmmrec_bwd_<name>.so
-    (default: the MMREC_BWD_NT set above)"""
-    variants = dict(sp.split("=", 1) for sp in specs) if specs else VARIANTS
+def build_variants(specs):
+    """python tools/prof_linear.py build-variants name=-DFLAG[,-DFLAG] ...   (here, no GPU): tools/probe_libs/libmmrec_bwd_<name>.so,
+    the library with gemm.hip compiled with the extra flags.  There is no default set: gemm.hip has no compile-time switches
+    left (the closed A/Bs are in EXPERIMENTS.md and profiles/), so a variant is a macro of an experiment in progress."""
+    if not specs:
+        raise SystemExit("build-variants: give at least one name=-DFLAG[,-DFLAG]")
+    variants = dict(sp.split("=", 1) for sp in specs)
     import subprocess
     from mmrec_amd import build as b
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "probe_libs")
@@ -83,10 +82,13 @@ def build_variants(specs=()):
 
 
 def run_variants(shapes):
-    """python tools/prof_linear.py run-variants [shapes...]   (GPU): every variant library in its own process, twice"""
+    """MMREC_VARIANTS=a,b python tools/prof_linear.py run-variants [shapes...]   (GPU): every named variant library (built by
+    build-variants) in its own process, twice"""
     import subprocess
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "probe_libs")
-    names = os.environ["MMREC_VARIANTS"].split(",") if os.environ.get("MMREC_VARIANTS") else list(VARIANTS)   # (built by build-variants name=flags)
+    if not os.environ.get("MMREC_VARIANTS"):
+        raise SystemExit("run-variants: name the variants in MMREC_VARIANTS=a,b")
+    names = os.environ["MMREC_VARIANTS"].split(",")
     for rnd in range(2):
         for name in names:
             env = dict(os.environ, MMREC_HIP_LIB=os.path.join(out, "libmmrec_bwd_%s.so" % name))

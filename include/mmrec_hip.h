@@ -805,6 +805,69 @@ int mmrec_posterior_fusion_bwd_f32(const float* mu_v, const float* lv_v, const f
                                    const float* gZ, const float* g_kl, int64_t n, int32_t d, float* d_mu_v, float* d_lv_v,
                                    float* d_mu_t, float* d_lv_t, float* d_mu_c, float* d_lv_c, mmrec_stream_t stream);
 
+/* MVGAE's encoder heads over [n, 64] tables: H graph-convolution heads (mean, log-variance) that share ONE aggregated table, each
+ * with its output Linear and its skip Linear, with the backward.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: g_layer_k(leaky(conv_embed_k(x, graph))) + leaky(linear_layer_k(x)) for k = 4, 5 -- mvgae.py, the end of GCN.forward
+ *           -- and autograd's mirror of it, given AX = spmm(graph, x): the aggregation is linear, spmm(graph, x W) = AX W.
+ * Served: d == 64, 1 <= H <= 4, n <= 2^30, fp32 row-major; anything else: MMREC_ERR_UNSUPPORTED, checked first.
+ *
+ * AX, X [n, 64];  W [H][64][64] as [in][out] (BaseModel.weight);  G, L [H][64][64] as torch's [out][in];  b, bg, bl [H][64];
+ * scale [H][n][64], the dropout mask already divided by the keep rate, or NULL (no dropout);  out [H][n][64].  eps = 1e-12f.
+ * Per head h and row, leaky(z) = z > 0 ? z : slope z:
+ *   a = AX W_h + b_h,  nrm = max(||a||_2, eps),  u = a / nrm,  d = u scale_h,  hh = leaky(d)
+ *   p = X L_h^T + bl_h,                                                        out_h = hh G_h^T + bg_h + leaky(p)
+ *
+ * THE PLAN.  One workgroup per block of mmrec_encoder_heads_rows_per_block(n) consecutive rows (64 ceil(n / 16,384): a multiple
+ * of 64, a function of n alone, at most 256 blocks), walked in tiles of 64 rows.  The HEAD LOOP IS OUTERMOST inside the
+ * workgroup: head h's three matrices are staged in LDS, the block's tiles are walked, then head h + 1.  All arithmetic is fp32;
+ * every operation named below is ONE rounding (an fma is one; sqrtf and / are correctly rounded), in this order (where a product
+ * feeds only an addition the compiler may contract the two into one fma: a rounding fewer, never one more):
+ *   a, p     a chain of 64 fma over the input column k ascending, started at the bias (b_h, bl_h).
+ *   norm     over the columns c = 4 l, 4 l + 1, 4 l + 2, 4 l + 3 (l = 0 .. 15): ss = fma(a_c, a_c, ss) from 0, then the 16 partial
+ *            sums by a butterfly (xor 8, 4, 2, 1): 4 + 4 roundings;  raw = sqrtf(ss), nrm = fmaxf(raw, eps), u = a / nrm,
+ *            d = u * scale (scale NULL: d = u, no rounding),  hh = d > 0 ? d : slope * d.
+ *   out      a chain of 64 fma over hh's column ascending, started at bg_h; then lp = p > 0 ? p : slope * p and ONE addition
+ *            out = chain + lp.
+ * mmrec_encoder_heads_fwd_f32: ONE launch; AX and X read once per head, out written once.
+ * mmrec_encoder_heads_bwd_f32: given g [H][n][64].  Every intermediate above is RECOMPUTED from the operands: the state between
+ *   the two calls is the operands and scale.  Then, per head and element,
+ *   dhh = a chain of 64 fma of g G_h over the output column o ascending, from 0;
+ *   du = (dhh * (d > 0 ? 1 : slope)) * scale  (scale NULL: the first product alone; d == 0 takes slope, as torch does; a dropped
+ *        entry, scale == 0, has du = 0 exactly whatever its sign);
+ *   dot = fma(u_c, du_c, dot) over the columns and butterfly of ss;
+ *   da = fma(-u, dot, du) / nrm  where raw >= eps;   da = du / nrm = du / eps  where raw < eps (the clamp holds the denominator
+ *        constant, as F.normalize's backward does);                              dp = g * (p > 0 ? 1 : slope);
+ *   dAX = ONE chain of 64 H fma from 0: head 0's 64 terms da[o] W_0[k][o], o ascending, then head 1's, ...  (each head's
+ *        workgroup pass stores the rows and the next pass, the same thread, continues from the stored value);
+ *   dX  = ONE chain of 64 H fma from 0 alike, of the terms dp[o] L_h[o][k].
+ *   Weight gradients, per block and head: dW_h[k][o] is ONE fma chain from 0 over the block's rows r ascending of AX[r][k] da[r][o]:
+ *   rows_per_block roundings;  dG_h[o][k] alike of g[r][o] hh[r][k];  dL_h[o][k] alike of dp[r][o] X[r][k].  db_h (terms da),
+ *   dbg_h (g), dbl_h (dp): the rows 4 q .. 4 q + 3 of each tile are added in order onto one sum per group q of a tile's 16, from 0
+ *   (rows_per_block / 16 additions), then the 16 groups in order from 0 (16).  The main pass leaves one partial of
+ *   3 (64 64 + 64) = 12,480 floats per block and head in the workspace ([block][head][dW | dG | dL | db | dbg | dbl]); the finish
+ *   (a second launch, NOT made where no weight gradient is wanted) adds, per output, the blocks j, j + 4, j + 8, ... in order
+ *   from 0 for j = 0 .. 3 and then the four sums in order: ceil(blocks / 4) + 3 roundings.
+ *   Rows past n are zeros in every tile (g too): they add exact zeros to every sum and are never stored; their scale is not read.
+ *   Any of the eight outputs may be NULL (not computed; the three weight gradient chains run if any of the six is wanted); all
+ *   eight NULL: 0, no launch.
+ * NO ATOMICS, every order fixed by n and H alone: two calls on the same inputs give the same bits.
+ * workspace: mmrec_encoder_heads_workspace_bytes(n, H) bytes (16-byte aligned), 12,480 H floats per block (51.2 MB at most); 0
+ * for n < 0, n > 2^30 or H outside 1 .. 4; needed only where a weight gradient is wanted.  Outputs must not alias inputs.
+ * d != 64, H outside 1 .. 4 or n > 2^30: MMREC_ERR_UNSUPPORTED; n < 0: MMREC_ERR_BAD_ARG; n == 0: 0, no launch, nothing touched;
+ * a NULL operand other than scale, a NULL out or g, or a NULL workspace where a weight gradient is wanted: MMREC_ERR_BAD_ARG --
+ * in this order, before any pointer is followed.  No synchronisation, no allocation, no data-dependent launch shape or address,
+ * capture-safe (the first call on a device raises the kernels' LDS limit: make one call before capturing). */
+int32_t mmrec_encoder_heads_rows_per_block(int64_t n);
+size_t mmrec_encoder_heads_workspace_bytes(int64_t n, int32_t H);
+int mmrec_encoder_heads_fwd_f32(const float* AX, const float* X, const float* W, const float* b, const float* G, const float* bg,
+                                const float* L, const float* bl, const float* scale, int64_t n, int32_t d, int32_t H, float slope,
+                                float* out, mmrec_stream_t stream);
+int mmrec_encoder_heads_bwd_f32(const float* AX, const float* X, const float* W, const float* b, const float* G, const float* bg,
+                                const float* L, const float* bl, const float* scale, const float* g, int64_t n, int32_t d,
+                                int32_t H, float slope, float* dAX, float* dX, float* dW, float* db, float* dG, float* dbg,
+                                float* dL, float* dbl, void* workspace, mmrec_stream_t stream);
+
 /* Top-k of a mix of three row softmaxes against three whole tables, never storing a [B, N] block: DAMRS's pseudo-labels.
  * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
  * replaces: topk(p_a + p_b + 2 p_m, 10) with p = softmax(normalize(h[ids]) @ normalize(h).T, dim=1) for each of three

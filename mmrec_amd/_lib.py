@@ -101,6 +101,10 @@ SIGNATURES = {
     "mmrec_posterior_fusion_workspace_bytes": (c_size_t, [c_int64]),
     "mmrec_posterior_fusion_fwd_f32": (c_int32, [_P] * 10 + [c_int64, c_int32, _P, _P, _P, _P, _P]),
     "mmrec_posterior_fusion_bwd_f32": (c_int32, [_P] * 12 + [c_int64, c_int32] + [_P] * 7),
+    "mmrec_encoder_heads_rows_per_block": (c_int32, [c_int64]),
+    "mmrec_encoder_heads_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "mmrec_encoder_heads_fwd_f32": (c_int32, [_P] * 9 + [c_int64, c_int32, c_int32, c_float, _P, _P]),
+    "mmrec_encoder_heads_bwd_f32": (c_int32, [_P] * 10 + [c_int64, c_int32, c_int32, c_float] + [_P] * 10),
     "mmrec_tri_topk_split_cols": (c_int32, [c_int32, c_int32]),
     "mmrec_tri_topk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mmrec_tri_topk_f32": (c_int32, [_P, _P, _P, c_int32, _P, c_int32, _P, _P, c_int32, _P, _P, _P, _P]),

@@ -3196,6 +3196,97 @@ def posterior_fusion(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# MVGAE's encoder heads (csrc/encoder_heads.hip): H normalised convolutions of one aggregated table, output and skip Linears
+# ------------------------------------------------------------------------------------------------
+ENCODER_HEADS = True   # False: every encoder_heads call is `encoder_heads_torch` (A/B runs)
+ENCODER_HEADS_MAX = 4  # heads one call serves
+
+
+def encoder_heads_rows_per_block(n):
+    """rows of a table of n rows that one workgroup of the encoder heads kernels walks (the library's plan)"""
+    return int(_lib.load().mmrec_encoder_heads_rows_per_block(int(n)))
+
+
+def encoder_heads_torch(AX, X, W, b, G, bg, L, bl, scale=None, slope=0.01):
+    """The end of MVGAE's GCN.forward (models/mvgae.py, the `fused_heads` key off) as a function of AX = spmm(graph, x), x and
+    the stacked parameters of H heads, in stock torch -> out [H, n, d]: a = AX W_h + b_h, u = normalize(a), d = u scale_h,
+    out_h = leaky(d) G_h^T + bg_h + leaky(X L_h^T + bl_h).  The composition `encoder_heads` falls back to."""
+    fn = torch.nn.functional
+    u = fn.normalize(torch.matmul(AX, W) + b.unsqueeze(1), p=2, dim=-1)
+    hh = fn.leaky_relu(u if scale is None else u * scale, slope)
+    p = torch.matmul(X, L.transpose(1, 2)) + bl.unsqueeze(1)
+    return torch.matmul(hh, G.transpose(1, 2)) + bg.unsqueeze(1) + fn.leaky_relu(p, slope)
+
+
+def encoder_heads_served(AX, X, W, b, G, bg, L, bl, scale=None, slope=0.01):
+    """True where `encoder_heads` runs the kernels: device fp32 contiguous [n, 64] tables AX and X of one shape, 1 <= n <= 2^30,
+    device fp32 contiguous [H, 64, 64] matrices and [H, 64] biases with H in 1 .. 4, `scale` None or such a [H, n, 64] tensor,
+    all on one device, the `ENCODER_HEADS` switch on."""
+    def ok(t, shape):
+        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                    tuple(t.shape) == shape)
+
+    def table(t):
+        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
+    if not (ENCODER_HEADS and table(AX) and table(X) and AX.shape == X.shape and isinstance(W, torch.Tensor) and W.dim() == 3):
+        return False
+    H, n = W.shape[0], AX.shape[0]
+    if not 1 <= H <= ENCODER_HEADS_MAX:
+        return False
+    if scale is not None and not ok(scale, (H, n, EMB_DIM)):
+        return False
+    others = (X, W, b, G, bg, L, bl) + (() if scale is None else (scale,))
+    return bool(all(ok(w, (H, EMB_DIM, EMB_DIM)) for w in (W, G, L)) and all(ok(v, (H, EMB_DIM)) for v in (b, bg, bl)) and
+                all(t.device == AX.device for t in others))
+
+
+class _EncoderHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, AX, X, W, b, G, bg, L, bl, scale, slope):
+        ops = (AX, X, W, b, G, bg, L, bl)
+        n, H = AX.shape[0], W.shape[0]
+        out = torch.empty((H, n, EMB_DIM), dtype=AX.dtype, device=AX.device)
+        _lib.check(_lib.load().mmrec_encoder_heads_fwd_f32(*[_p(t) for t in ops], _p(scale), n, EMB_DIM, H, float(slope), _p(out),
+                                                           _stream()), "encoder_heads_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.slope = float(slope)
+        ctx.save_for_backward(*ops, scale)                           # every intermediate is recomputed: nothing else is kept
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        *ops, scale = ctx.saved_tensors
+        want = ctx.needs_input_grad[:8]
+        if not any(want) or g is None:
+            return (None,) * 10
+        lib = _lib.load()
+        n, H = ops[0].shape[0], ops[2].shape[0]
+        g = g.contiguous()
+        grads = [torch.empty_like(t) if w else None for t, w in zip(ops, want)]
+        ws = _ws(lib.mmrec_encoder_heads_workspace_bytes(n, H), ops[0].device) if any(want[2:]) else None
+        _lib.check(lib.mmrec_encoder_heads_bwd_f32(*[_p(t) for t in ops], _p(scale), _p(g), n, EMB_DIM, H, ctx.slope,
+                                                   *[_p(t) for t in grads], _p(ws), _stream()), "encoder_heads_bwd")
+        return tuple(grads) + (None, None)
+
+
+def encoder_heads(AX, X, W, b, G, bg, L, bl, scale=None, slope=0.01):
+    """MVGAE's encoder heads (mvgae.py, the end of GCN.forward) -> out [H, n, 64], one table per head (mean, log-variance):
+    a = AX W_h + b_h, u = a / max(||a||, 1e-12), d = u scale_h, out_h = leaky(d) G_h^T + bg_h + leaky(X L_h^T + bl_h);  AX =
+    spmm(graph, x) and X = x [n, 64]; W [H, 64, 64] the stacked BaseModel.weight ([in][out]), G and L [H, 64, 64] the stacked
+    g_layer and linear_layer weights as nn.Linear keeps them, b, bg, bl [H, 64]; `scale` [H, n, 64] the dropout masks already
+    divided by the keep rate (None: no dropout).  Differentiable in the first eight operands; `scale` gets no gradient.
+    Served by the kernels (`encoder_heads_served`): one launch forward, two backward (the main pass and the finish that adds the
+    blocks' weight-gradient partials in a fixed order); the heads are walked one after another inside each workgroup, every
+    intermediate kept in LDS and RECOMPUTED in the backward, so the state between the calls is the operands and `scale`.  An
+    operand that needs no gradient is not computed.  No atomics: the same bits every call, so `DETERMINISTIC` changes nothing.
+    EVERY OTHER CASE (CPU tensors, a width other than 64, other dtypes, non-contiguous operands, an empty table, more than four
+    heads, the switch off) is `encoder_heads_torch` with stock autograd."""
+    if encoder_heads_served(AX, X, W, b, G, bg, L, bl, scale, slope):
+        return _EncoderHeads.apply(AX, X, W, b, G, bg, L, bl, scale, slope)
+    return encoder_heads_torch(AX, X, W, b, G, bg, L, bl, scale, slope)
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

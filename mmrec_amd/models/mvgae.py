@@ -28,6 +28,12 @@ launches forward, one backward, every intermediate recomputed) for the four z ta
 `result_embed`; the four noise tables are drawn in the composition's order (pd, v, t, c); and the four reconstruction
 terms become one batched term: the 3 B rows of cat(user, pos, neg) are gathered from the four z tables FIRST, the sigmoid
 runs on those [4, 3 B, 64] rows only, then one bmm and one row maximum.  The loss is the same sum.
+
+With the config key `fused_heads: True` (absent / False: the four lines at the end of `GCN.forward`, untouched; independent of
+`fused_posterior`) every encoder ends with ONE aggregation AX = spmm(graph, x) for both heads -- the aggregation is linear, so
+spmm(graph, x W) = AX W -- and one `hip_ops.encoder_heads` call (csrc/encoder_heads.hip: one launch forward, two backward) for
+the two normalised convolutions, their dropouts (two masks drawn in the composition's order, mu then logvar), the four
+leaky-ReLUs and the four 64 x 64 Linears.  The trunk convolutions stay as they are: conv_embed_1 is 128 wide.
 """
 import math
 
@@ -78,9 +84,9 @@ class BaseModel(nn.Module):
 
 
 class GCN(nn.Module):
-    def __init__(self, features, num_user, dim_id, num_layer, dim_latent, device):
+    def __init__(self, features, num_user, dim_id, num_layer, dim_latent, device, fused_heads=False):
         super().__init__()
-        self.features, self.num_layer = features, num_layer
+        self.features, self.num_layer, self.fused_heads = features, num_layer, fused_heads
         self.preference = nn.init.xavier_normal_(torch.rand((num_user, dim_latent))).to(device)    # not a Parameter
         self.MLP = nn.Linear(features.size(1), dim_latent)
         nn.init.xavier_normal_(self.MLP.weight)
@@ -112,11 +118,27 @@ class GCN(nn.Module):
             x = F.leaky_relu(_lin64(self.g_layer1, F.leaky_relu(self.conv_embed_1(x, graph))))
         if self.num_layer > 1:
             x = F.leaky_relu(_lin64(self.g_layer2, F.leaky_relu(self.conv_embed_2(x, graph))))
+        if self.fused_heads:
+            return self._fused_heads(x.contiguous(), graph)
         mu = F.leaky_relu(self.conv_embed_4(x, graph))
         mu = _lin64(self.g_layer4, mu) + F.leaky_relu(_lin64(self.linear_layer4, x))
         logvar = F.leaky_relu(self.conv_embed_5(x, graph))
         logvar = _lin64(self.g_layer5, logvar) + F.leaky_relu(_lin64(self.linear_layer5, x))
         return mu, logvar
+
+    def _fused_heads(self, x, graph):
+        """the four lines below it in `forward` with the `fused_heads` key on: one aggregation for both heads, then one op"""
+        ax = hip_ops.spmm(graph, x)
+        scale = None
+        if self.training:                                              # the composition's call order: mu, then logvar
+            scale = torch.stack([F.dropout(torch.ones_like(ax), p=0.1, training=True) for _ in range(2)])
+        heads = [(getattr(self, 'conv_embed_%d' % j), getattr(self, 'g_layer%d' % j), getattr(self, 'linear_layer%d' % j))
+                 for j in (4, 5)]
+        stack = lambda ts: torch.stack(list(ts))                       # noqa: E731
+        out = hip_ops.encoder_heads(ax, x, stack(c.weight for c, _, _ in heads), stack(c.bias for c, _, _ in heads),
+                                    stack(g.weight for _, g, _ in heads), stack(g.bias for _, g, _ in heads),
+                                    stack(l.weight for _, _, l in heads), stack(l.bias for _, _, l in heads), scale)
+        return out[0], out[1]
 
 
 def product_of_experts(mu, logvar, eps=1e-8):
@@ -134,15 +156,16 @@ class MVGAE(FusedEvalMixin, GeneralRecommender):
         self.dim_x = config['embedding_size']
         self.beta = config['beta']
         self.fused_posterior = bool(config['fused_posterior']) if 'fused_posterior' in config else False    # new key, default off
+        self.fused_heads = bool(config['fused_heads']) if 'fused_heads' in config else False                # new key, default off
         num_layer = config['n_layers']
         if self.v_feat is None or self.t_feat is None:
             raise ValueError("MVGAE needs image and text features (its forward reads both encoders)")
         self.collaborative = nn.init.xavier_normal_(torch.rand((self.n_items, self.dim_x))).to(self.device)
         inter = dataset.inter_matrix(form='coo').astype(np.float32)
         self.graph = self_loop_mean_graph(inter, self.n_users, self.n_items, self.device)
-        self.v_gcn = GCN(self.v_feat, self.n_users, self.dim_x, num_layer, 128, self.device)
-        self.t_gcn = GCN(self.t_feat, self.n_users, self.dim_x, num_layer, 128, self.device)
-        self.c_gcn = GCN(self.collaborative, self.n_users, self.dim_x, num_layer, 128, self.device)
+        self.v_gcn = GCN(self.v_feat, self.n_users, self.dim_x, num_layer, 128, self.device, self.fused_heads)
+        self.t_gcn = GCN(self.t_feat, self.n_users, self.dim_x, num_layer, 128, self.device, self.fused_heads)
+        self.c_gcn = GCN(self.collaborative, self.n_users, self.dim_x, num_layer, 128, self.device, self.fused_heads)
         n = self.n_users + self.n_items
         self.result_embed = nn.init.xavier_normal_(torch.rand((n, self.dim_x))).to(self.device)
 

@@ -868,6 +868,63 @@ int mmrec_encoder_heads_bwd_f32(const float* AX, const float* X, const float* W,
                                 int32_t H, float slope, float* dAX, float* dX, float* dW, float* db, float* dG, float* dbg,
                                 float* dL, float* dbl, void* workspace, mmrec_stream_t stream);
 
+/* MMGCN's 64-wide layer over [n, 64] tables: the graph convolution, the skip Linear with the id embedding and the 128 -> 64 Linear
+ * over their concatenation, with the backward.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: h = leaky(conv_embed_k(x, graph)), x_hat = leaky(linear_layer_k(x)) + id_embedding,
+ *           x = leaky(g_layer_k(cat(h, x_hat))) for k = 2, 3 -- mmgcn.py, GCN.forward -- and autograd's mirror of it, given
+ *           AX = spmm(graph, x): the aggregation is linear, spmm(graph, x Wc) = AX Wc.
+ * Served: d == 64, slope > 0, n <= 2^30, fp32 row-major; anything else: MMREC_ERR_UNSUPPORTED, checked first.
+ *
+ * AX, X [n, 64];  R [n, 64] (the id embedding's rows) or NULL (zeros);  Wc [64][64] as [in][out] (BaseModel.weight);  Wl [64][64]
+ * and Wg [64][128] as torch's [out][in], Wg = [Gh | Gx] with Gh = Wg[:, :64] and Gx = Wg[:, 64:];  bl, bg [64];  out [n, 64].
+ * Per row, leaky(z) = z > 0 ? z : slope z:
+ *   a = AX Wc,  h = leaky(a);    p = X Wl^T + bl,  xh = leaky(p) + R;    q = h Gh^T + xh Gx^T + bg;    out = leaky(q)
+ *
+ * THE PLAN.  One workgroup per block of mmrec_gcn_layer_rows_per_block(n) consecutive rows (64 ceil(n / 16,384): a multiple of 64,
+ * a function of n alone, at most 256 blocks), walked in tiles of 64 rows.  All arithmetic is fp32; every operation named below is
+ * ONE rounding (an fma is one), in this order (where a product feeds only an addition the compiler may contract the two into one
+ * fma: a rounding fewer, never one more):
+ *   a        a chain of 64 fma over the input column k ascending, started at 0;   h = a > 0 ? a : slope * a.
+ *   p        a chain of 64 fma over the input column k ascending, started at bl;  xh = (p > 0 ? p : slope * p) + R: ONE addition
+ *            (R NULL: none).
+ *   q        ONE chain of 128 fma started at bg: the 64 terms h[k] Gh[c][k], k ascending, then the 64 terms xh[k] Gx[c][k],
+ *            k ascending;  out = q > 0 ? q : slope * q.
+ * mmrec_gcn_layer_fwd_f32: ONE launch; AX, X and R read once, out written once.
+ * mmrec_gcn_layer_bwd_f32: given g [n][64] and the forward's out.  a, h, p, xh are RECOMPUTED as above: the state between the two
+ *   calls is the operands and out.  Then, per element,
+ *   dq  = g * (out > 0 ? 1 : slope)   (the sign of out is the sign of q, since slope > 0; out == 0 takes slope, as torch does);
+ *   dh  = a chain of 64 fma of dq Gh over the output column c ascending, from 0;   da = dh * (a > 0 ? 1 : slope);
+ *   dxh = a chain of 64 fma of dq Gx over the output column c ascending, from 0;   dp = dxh * (p > 0 ? 1 : slope);   dR = dxh;
+ *   dAX = a chain of 64 fma from 0 of the terms da[o] Wc[k][o], o ascending;   dX = alike of the terms dp[o] Wl[o][k].
+ *   Weight gradients, per block: dWc[k][o] is ONE fma chain from 0 over the block's rows r ascending of AX[r][k] da[r][o]:
+ *   rows_per_block roundings;  dWl[o][k] alike of dp[r][o] X[r][k];  dWg[c][k] alike of dq[r][c] h[r][k] and dWg[c][64 + k] of
+ *   dq[r][c] xh[r][k].  dbg (terms dq), dbl (dp): the rows 4 j .. 4 j + 3 of each tile are added in order onto one sum per group
+ *   j of a tile's 16, from 0 (rows_per_block / 16 additions), then the 16 groups in order from 0 (16).  The main pass leaves one
+ *   partial of 4 (64 64) + 2 (64) = 16,512 floats per block in the workspace ([block][dWc | dGh | dWl | dGx | dbg | dbl]); the
+ *   finish (a second launch, NOT made where no weight gradient is wanted) adds, per output, the blocks j, j + 4, j + 8, ... in
+ *   order from 0 for j = 0 .. 3 and then the four sums in order: ceil(blocks / 4) + 3 roundings.
+ *   Rows past n are zeros in every tile of AX, X, g and out: they add exact zeros to every sum and are never stored; their R is
+ *   not read.
+ *   Any of the eight outputs may be NULL (not computed; the four weight gradient chains run if any of the five is wanted); all
+ *   eight NULL: 0, no launch.
+ * NO ATOMICS, every order fixed by n alone: two calls on the same inputs give the same bits.
+ * workspace: mmrec_gcn_layer_workspace_bytes(n) bytes (16-byte aligned), 16,512 floats per block (16.9 MB at most); 0 for n < 0
+ * or n > 2^30; needed only where a weight gradient is wanted.  Outputs must not alias inputs.
+ * d != 64, slope <= 0 (or NaN) or n > 2^30: MMREC_ERR_UNSUPPORTED; n < 0: MMREC_ERR_BAD_ARG; n == 0: 0, no launch, nothing
+ * touched; a NULL operand other than R, a NULL out or g, or a NULL workspace where a weight gradient is wanted:
+ * MMREC_ERR_BAD_ARG -- in this order, before any pointer is followed.  No synchronisation, no allocation, no data-dependent
+ * launch shape or address, capture-safe (the first call on a device raises the kernels' LDS limit: make one call before
+ * capturing). */
+int32_t mmrec_gcn_layer_rows_per_block(int64_t n);
+size_t mmrec_gcn_layer_workspace_bytes(int64_t n);
+int mmrec_gcn_layer_fwd_f32(const float* AX, const float* X, const float* R, const float* Wc, const float* Wl, const float* bl,
+                            const float* Wg, const float* bg, int64_t n, int32_t d, float slope, float* out, mmrec_stream_t stream);
+int mmrec_gcn_layer_bwd_f32(const float* AX, const float* X, const float* R, const float* Wc, const float* Wl, const float* bl,
+                            const float* Wg, const float* bg, const float* out, const float* g, int64_t n, int32_t d, float slope,
+                            float* dAX, float* dX, float* dR, float* dWc, float* dWl, float* dbl, float* dWg, float* dbg,
+                            void* workspace, mmrec_stream_t stream);
+
 /* Top-k of a mix of three row softmaxes against three whole tables, never storing a [B, N] block: DAMRS's pseudo-labels.
  * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
  * replaces: topk(p_a + p_b + 2 p_m, 10) with p = softmax(normalize(h[ids]) @ normalize(h).T, dim=1) for each of three

@@ -105,6 +105,10 @@ SIGNATURES = {
     "mmrec_encoder_heads_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "mmrec_encoder_heads_fwd_f32": (c_int32, [_P] * 9 + [c_int64, c_int32, c_int32, c_float, _P, _P]),
     "mmrec_encoder_heads_bwd_f32": (c_int32, [_P] * 10 + [c_int64, c_int32, c_int32, c_float] + [_P] * 10),
+    "mmrec_gcn_layer_rows_per_block": (c_int32, [c_int64]),
+    "mmrec_gcn_layer_workspace_bytes": (c_size_t, [c_int64]),
+    "mmrec_gcn_layer_fwd_f32": (c_int32, [_P] * 8 + [c_int64, c_int32, c_float, _P, _P]),
+    "mmrec_gcn_layer_bwd_f32": (c_int32, [_P] * 10 + [c_int64, c_int32, c_float] + [_P] * 10),
     "mmrec_tri_topk_split_cols": (c_int32, [c_int32, c_int32]),
     "mmrec_tri_topk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mmrec_tri_topk_f32": (c_int32, [_P, _P, _P, c_int32, _P, c_int32, _P, _P, c_int32, _P, _P, _P, _P]),

@@ -33,6 +33,26 @@ __device__ __forceinline__ void t64_matrix(float* __restrict__ L, const float* _
     }
 }
 
+// the same of a [64][64] block whose rows lie ld floats apart (ld a multiple of 4: one half of a [64][128] matrix)
+__device__ __forceinline__ void t64_matrix_ld(float* __restrict__ L, const float* __restrict__ g, int ld) {
+    for (int e = threadIdx.x; e < T64 * T64 / 4; e += T64_BLOCK) {
+        const int r = e / 16, c = 4 * (e % 16);
+        *reinterpret_cast<float4*>(L + r * T64_LD + c) = *reinterpret_cast<const float4*>(g + (size_t)r * ld + c);
+    }
+}
+
+// ... and TRANSPOSED: L[c][r] = g[r ld + c]
+__device__ __forceinline__ void t64_matrix_ld_t(float* __restrict__ L, const float* __restrict__ g, int ld) {
+    for (int e = threadIdx.x; e < T64 * T64 / 4; e += T64_BLOCK) {
+        const int r = e / 16, c = 4 * (e % 16);
+        const float4 v = *reinterpret_cast<const float4*>(g + (size_t)r * ld + c);
+        L[c * T64_LD + r] = v.x;
+        L[(c + 1) * T64_LD + r] = v.y;
+        L[(c + 2) * T64_LD + r] = v.z;
+        L[(c + 3) * T64_LD + r] = v.w;
+    }
+}
+
 // rows row0 .. row0 + 63 of a [n, 64] table into a row-major tile; rows past n, and a NULL table, read as zeros
 __device__ __forceinline__ void t64_load(float* __restrict__ R, const float* __restrict__ g, long row0, long n, int rg, int sg) {
 #pragma unroll

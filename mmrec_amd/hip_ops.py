@@ -3287,6 +3287,92 @@ def encoder_heads(AX, X, W, b, G, bg, L, bl, scale=None, slope=0.01):
 
 
 # ------------------------------------------------------------------------------------------------
+# MMGCN's 64-wide layer (csrc/gcn_layer.hip): convolution, skip Linear + id embedding and the 128 -> 64 Linear over their cat
+# ------------------------------------------------------------------------------------------------
+GCN_LAYER = True   # False: every gcn_layer call is `gcn_layer_torch` (A/B runs)
+
+
+def gcn_layer_rows_per_block(n):
+    """rows of a table of n rows that one workgroup of the GCN layer kernels walks (the library's plan)"""
+    return int(_lib.load().mmrec_gcn_layer_rows_per_block(int(n)))
+
+
+def gcn_layer_torch(AX, X, R, Wc, Wl, bl, Wg, bg, slope=0.01):
+    """One layer of MMGCN's GCN.forward (models/mmgcn.py, the `fused_layers` key off) as a function of AX = spmm(graph, x), x,
+    the id embedding R (or None) and the layer's parameters, in stock torch -> [n, d]: h = leaky(AX Wc), xh = leaky(X Wl^T + bl)
+    + R, out = leaky(cat(h, xh) Wg^T + bg).  The composition `gcn_layer` falls back to."""
+    fn = torch.nn.functional
+    h = fn.leaky_relu(torch.matmul(AX, Wc), slope)
+    xh = fn.leaky_relu(fn.linear(X, Wl, bl), slope)
+    if R is not None:
+        xh = xh + R
+    return fn.leaky_relu(fn.linear(torch.cat((h, xh), dim=1), Wg, bg), slope)
+
+
+def gcn_layer_served(AX, X, R, Wc, Wl, bl, Wg, bg, slope=0.01):
+    """True where `gcn_layer` runs the kernels: device fp32 contiguous [n, 64] tables AX, X and R (or R None) of one shape,
+    1 <= n <= 2^30, device fp32 contiguous Wc, Wl [64, 64], Wg [64, 128] and bl, bg [64], all on one device, slope > 0, the
+    `GCN_LAYER` switch on."""
+    def ok(t, shape):
+        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                    tuple(t.shape) == shape and t.device == AX.device)
+
+    def table(t):
+        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
+    if not (GCN_LAYER and table(AX) and table(X) and AX.shape == X.shape and float(slope) > 0.0):
+        return False
+    if X.device != AX.device or (R is not None and not ok(R, tuple(AX.shape))):
+        return False
+    return bool(ok(Wc, (EMB_DIM, EMB_DIM)) and ok(Wl, (EMB_DIM, EMB_DIM)) and ok(Wg, (EMB_DIM, 2 * EMB_DIM)) and
+                ok(bl, (EMB_DIM,)) and ok(bg, (EMB_DIM,)))
+
+
+class _GcnLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, AX, X, R, Wc, Wl, bl, Wg, bg, slope):
+        ops = (AX, X, R, Wc, Wl, bl, Wg, bg)
+        n = AX.shape[0]
+        out = torch.empty((n, EMB_DIM), dtype=AX.dtype, device=AX.device)
+        _lib.check(_lib.load().mmrec_gcn_layer_fwd_f32(*[_p(t) for t in ops], n, EMB_DIM, float(slope), _p(out), _stream()),
+                   "gcn_layer_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.slope = float(slope)
+        ctx.save_for_backward(*ops, out)                             # a, h, p, xh are recomputed; q's sign is out's
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        *ops, out = ctx.saved_tensors
+        want = ctx.needs_input_grad[:8]
+        if not any(want) or g is None:
+            return (None,) * 9
+        lib = _lib.load()
+        n = ops[0].shape[0]
+        g = g.contiguous()
+        grads = [torch.empty_like(t) if w and t is not None else None for t, w in zip(ops, want)]
+        ws = _ws(lib.mmrec_gcn_layer_workspace_bytes(n), ops[0].device) if any(x is not None for x in grads[3:]) else None
+        _lib.check(lib.mmrec_gcn_layer_bwd_f32(*[_p(t) for t in ops], _p(out), _p(g), n, EMB_DIM, ctx.slope,
+                                               *[_p(t) for t in grads], _p(ws), _stream()), "gcn_layer_bwd")
+        return tuple(grads) + (None,)
+
+
+def gcn_layer(AX, X, R, Wc, Wl, bl, Wg, bg, slope=0.01):
+    """One 64-wide layer of MMGCN's GCN.forward (mmgcn.py) -> [n, 64]: h = leaky(AX Wc), xh = leaky(X Wl^T + bl) + R,
+    out = leaky(h Gh^T + xh Gx^T + bg) with Wg = [Gh | Gx];  AX = spmm(graph, x) and X = x [n, 64]; R [n, 64] the id embedding
+    (None: zeros); Wc [64, 64] the BaseModel.weight ([in][out]), Wl [64, 64] and Wg [64, 128] the linear_layer and g_layer
+    weights as nn.Linear keeps them, bl, bg [64].  Differentiable in all eight operands.
+    Served by the kernels (`gcn_layer_served`): one launch forward, two backward (the main pass and the finish that adds the
+    blocks' weight-gradient partials in a fixed order); every intermediate is kept in LDS and RECOMPUTED in the backward, so the
+    state between the calls is the operands and the result.  An operand that needs no gradient is not computed.  No atomics: the
+    same bits every call, so `DETERMINISTIC` changes nothing.
+    EVERY OTHER CASE (CPU tensors, a width other than 64, other dtypes, non-contiguous operands, an empty table, a slope that
+    is not positive, the switch off) is `gcn_layer_torch` with stock autograd."""
+    if gcn_layer_served(AX, X, R, Wc, Wl, bl, Wg, bg, slope):
+        return _GcnLayer.apply(AX, X, R, Wc, Wl, bl, Wg, bg, slope)
+    return gcn_layer_torch(AX, X, R, Wc, Wl, bl, Wg, bg, slope)
+
+
+# ------------------------------------------------------------------------------------------------
 # Rows next to the hot path (SURVEY.md 8f): device negative sampler, device ranking metrics
 # ------------------------------------------------------------------------------------------------
 def flat_to_csr(flat, lens, device):

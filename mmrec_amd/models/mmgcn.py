@@ -7,6 +7,11 @@ features) and 64 -- no PyG, no scatter; its backward uses the transposed CSR.  T
 plain library GEMMs (torch -> hipBLASLt).  Reference quirks kept on purpose:
 `concate = 'False'` is a truthy string, so the concat branch is ON; `id_embedding` and `preference`
 are plain tensors, not Parameters, hence never trained; evaluation reuses the last training forward.
+
+With the config key `fused_layers: True` (absent / False: the loop of `GCN.forward`, untouched) every layer whose conv,
+linear_layer and g_layer are all 64 wide -- layers 2 and 3 -- aggregates FIRST, AX = spmm(graph, x): the aggregation is linear, so
+spmm(graph, x Wc) = AX Wc, and everything else in the layer is row-local.  It is one `hip_ops.gcn_layer` call
+(csrc/gcn_layer.hip: one launch forward, two backward) after the SpMM.  The same function up to fp32 rounding order.
 """
 import math
 
@@ -67,10 +72,17 @@ def _lin64(layer, x):
     return layer(x)
 
 
+def _layer_is_64(conv, lin, gl):
+    d = hip_ops.EMB_DIM
+    return (tuple(conv.weight.shape) == (d, d) and tuple(lin.weight.shape) == (d, d) and tuple(gl.weight.shape) == (d, 2 * d)
+            and lin.bias is not None and gl.bias is not None)
+
+
 class GCN(nn.Module):
-    def __init__(self, num_user, dim_feat, dim_id, dim_latent, device):
+    def __init__(self, num_user, dim_feat, dim_id, dim_latent, device, fused_layers=False):
         super().__init__()
         self.dim_latent = dim_latent
+        self.fused_layers = fused_layers
         d = dim_latent if dim_latent else dim_feat
         self.preference = nn.init.xavier_normal_(torch.rand((num_user, d))).to(device)   # not a Parameter
         if dim_latent:
@@ -98,6 +110,12 @@ class GCN(nn.Module):
         for conv, lin, gl in ((self.conv_embed_1, self.linear_layer1, self.g_layer1),
                               (self.conv_embed_2, self.linear_layer2, self.g_layer2),
                               (self.conv_embed_3, self.linear_layer3, self.g_layer3)):
+            if self.fused_layers and _layer_is_64(conv, lin, gl):
+                # the `fused_layers` key: aggregate first (spmm(graph, x Wc) = spmm(graph, x) Wc), the rest of the layer in one op
+                x = x.contiguous()
+                x = hip_ops.gcn_layer(hip_ops.spmm(graph, x), x, id_embedding, conv.weight, lin.weight, lin.bias, gl.weight,
+                                      gl.bias)
+                continue
             # every 64-wide layer runs on the MFMA projection kernels (forward, dW + db, dX): the
             # library's skinny dW GEMMs (contraction over 26k nodes) were 47 % of the step
             # h = leaky_relu(conv(x)), x_hat = leaky_relu(linear(x)) + id_embedding and their cat (mmgcn.py:170-173): one launch
@@ -116,6 +134,7 @@ class MMGCN(RelabelledIdsMixin, FusedEvalMixin, GeneralRecommender):
         dim_x = config['embedding_size']
         self.reg_weight = config['reg_weight']
         self.weight = torch.tensor([[1.0], [-1.0]]).to(self.device)
+        self.fused_layers = bool(config['fused_layers']) if 'fused_layers' in config else False      # new key, default off
         inter = dataset.inter_matrix(form='coo').astype(np.float32)
         self.graph = mean_aggregation_graph(inter, self.n_users, self.n_items, self.device)
         # new key `reorder` (models/_base.py): the modality graphs' node rows -- user preferences, item features, the id
@@ -129,10 +148,10 @@ class MMGCN(RelabelledIdsMixin, FusedEvalMixin, GeneralRecommender):
                 self.t_feat = self.t_feat.index_select(0, rl.inv_i.to(self.t_feat.device))
         self.num_modal = 0
         if self.v_feat is not None:
-            self.v_gcn = GCN(self.n_users, self.v_feat.size(1), dim_x, 256, self.device)
+            self.v_gcn = GCN(self.n_users, self.v_feat.size(1), dim_x, 256, self.device, self.fused_layers)
             self.num_modal += 1
         if self.t_feat is not None:
-            self.t_gcn = GCN(self.n_users, self.t_feat.size(1), dim_x, None, self.device)
+            self.t_gcn = GCN(self.n_users, self.t_feat.size(1), dim_x, None, self.device, self.fused_layers)
             self.num_modal += 1
         n = self.n_users + self.n_items
         self.id_embedding = nn.init.xavier_normal_(torch.rand((n, dim_x))).to(self.device)   # never trained

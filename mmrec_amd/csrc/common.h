@@ -29,6 +29,12 @@ __device__ __forceinline__ float f4_dot(float4 a, float4 b) {
     return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w)));
 }
 
+// sigmoid without overflow: exactly 1 / 0 once q underflows to 0; the argument of expf is exact and never positive
+__device__ __forceinline__ float stable_sigmoid(float z) {
+    const float q = expf(-fabsf(z));
+    return (z >= 0.f ? 1.f : q) / (1.f + q);
+}
+
 // x of lane (l ^ M), M a power of two, WITHOUT the LDS address path of __shfl_xor (which is a ds_bpermute_b32 plus the VALU
 // instructions that form its byte address -- every wave-level sort, reduction and broadcast of this library was made of them:
 // 196 in the warm bound kernel, 482 in the top-K final kernel): M = 1, 2 are DPP quad permutations (one VALU modifier), M = 4,

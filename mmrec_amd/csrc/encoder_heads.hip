@@ -6,11 +6,10 @@
 //     a = AX W_h + b_h, nrm = max(||a||, 1e-12), u = a / nrm, d = u scale_h, hh = leaky(d)
 //     p = X L_h^T + bl_h                                          out_h = hh G_h^T + bg_h + leaky(p)
 //
-// THE PLAN (what the fuzz's error bound counts).  One 256-thread workgroup per block of R = mmrec_encoder_heads_rows_per_block(n)
-// consecutive rows, walked as R / 64 tiles of 64 rows; the HEAD LOOP IS OUTERMOST: W_h, G_h, L_h are staged in LDS as they lie in
-// memory (68-float rows), the block's tiles are walked, then the next head.  Thread (rg, sg) of 16 x 16 owns the rows 4 rg .. + 3.
-//   stage   a 64-term fma chain per output, the summed index ascending, onto a given start (tile64.h): 64 roundings.
-//           a: over the input column from b;  p: from bl;  out: over hh's column from bg, then ONE addition of leaky(p).
+// THE PLAN (what the fuzz's error bound counts) is tile64.h's: blocks of R = mmrec_encoder_heads_rows_per_block(n) rows, stage,
+// weight partials, column sums, finish.  The HEAD LOOP IS OUTERMOST: W_h, G_h, L_h are staged in LDS as they lie in memory
+// (68-float rows), the block's tiles are walked, then the next head.  This op's own:
+//   stage   a: over the input column from b;  p: from bl;  out: over hh's column from bg, then ONE addition of leaky(p).
 //   norm    the thread's columns c = 4 sg .. 4 sg + 3: ss = fma(a_c, a_c, ss) from 0 in this order, then the butterfly over the 16
 //           lanes of the row (xor 8, 4, 2, 1); raw = sqrtf(ss), nrm = fmaxf(raw, 1e-12f), u = a / nrm, d = u * scale (scale NULL:
 //           d = u), leaky(z) = z > 0 ? z : slope * z.
@@ -21,11 +20,9 @@
 //   dAX = the stage of da W_h^T over the output column, started at 0 for head 0 and at the rows' dAX after head h - 1 for head h:
 //   one chain of 64 H terms, the heads in order;  dX = the stage of dp L_h over the output column, started and continued alike.
 //   dW_h[k][o] = one fma chain over the block's rows in order (AX^T da), dG_h[o][k] alike (g^T hh), dL_h[o][k] alike (dp^T X).
-//   The column sums db_h (da), dbg_h (g), dbl_h (dp): a thread adds its four rows in order, tile after tile, from 0; then the
-//   16 row groups are added in order from 0.
-//   Finish: thread (quarter, output) adds the blocks quarter, quarter + 4, ... in order from 0, then the four quarters in order.
-// NO ATOMICS, every order fixed by n and H alone.  Rows past n are zero in every tile (g too, so they add exact zeros to every sum;
-// their scale is never read) and are never stored.  The rows of dAX / dX that a later head adds onto were stored by the SAME thread.
+//   The column sums: db_h (da), dbg_h (g), dbl_h (dp).
+// Every order is fixed by n and H alone.  The scale of a row past n is never read.  The rows of dAX / dX that a later head adds
+// onto were stored by the SAME thread.
 // Workspace: per block and head 3 (64 64 + 64) = 12,480 floats: [dW][dG][dL][db][dbg][dbl].
 // LDS: 3 matrices + 3 tiles (forward) or + 6 tiles (backward) of 17,408 B, + 768 B of biases: 105,216 B and 157,440 B.
 #include "tile64.h"
@@ -33,21 +30,14 @@
 namespace {
 
 constexpr int EH_D = 64;
-constexpr int EH_MAX_BLOCKS = 256;
 constexpr int EH_MAX_HEADS = 4;
 constexpr int EH_W = EH_D * EH_D;
 constexpr int EH_PART = 3 * (EH_W + EH_D);                  // floats of one block's partial of one head
 constexpr int EH_VEC = 3 * EH_D;                            // b, bg, bl in LDS
 constexpr int EH_FWD_TILES = 3, EH_BWD_TILES = 6;
-constexpr int64_t EH_MAX_ROWS = (int64_t)1 << 30;
 constexpr float EH_EPS = 1e-12f;
 
 constexpr size_t eh_lds_bytes(int tiles) { return sizeof(float) * ((size_t)(3 + tiles) * T64_FLOATS + EH_VEC); }
-
-inline int eh_rows_per_block(int64_t n) { return t64_rows_per_block(n, EH_MAX_BLOCKS); }
-inline int eh_blocks(int64_t n) { return t64_blocks(n, EH_MAX_BLOCKS); }
-
-__device__ __forceinline__ float eh_leaky(float z, float slope) { return z > 0.f ? z : slope * z; }
 
 // head h's three matrices and three biases into LDS (visible after the caller's next barrier)
 __device__ __forceinline__ void eh_setup(float* __restrict__ LW, float* __restrict__ LG, float* __restrict__ LL,
@@ -64,13 +54,6 @@ __device__ __forceinline__ void eh_setup(float* __restrict__ LW, float* __restri
     }
 }
 
-// rows 4 rg + i at the columns 4 sg + j (layout L0) in registers to a row-major tile
-__device__ __forceinline__ void eh_put(float* __restrict__ R, int rg, int sg, const float (&v)[4][4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<float4*>(R + (4 * rg + i) * T64_LD + 4 * sg) = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
-}
-
 // the normalised convolution of the thread's rows at its columns 4 sg + j (layout L0), from the transposed AX tile
 struct EhRows {
     float u[4][4], d[4][4], sc[4][4];
@@ -80,8 +63,8 @@ struct EhRows {
 __device__ __forceinline__ void eh_recompute(const float* __restrict__ At, const float* __restrict__ LW,
                                              const float* __restrict__ vec, const float* __restrict__ scale, long row0, long n,
                                              int rg, int sg, EhRows& f) {
-    const float4 b4 = *reinterpret_cast<const float4*>(vec + 4 * sg);
-    float4 a[4] = {b4, b4, b4, b4};
+    float4 a[4];
+    t64_start0(a, vec, sg);
     t64_stage_nn(At, LW, rg, sg, a);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -122,7 +105,7 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_fwd_kernel(
         const float* __restrict__ scale_h = scale ? scale + (size_t)h * n * EH_D : nullptr;
         float* __restrict__ out_h = out + (size_t)h * n * EH_D;
         for (int t = 0; t < tiles; ++t) {
-            const long row0 = ((long)blockIdx.x * tiles + t) * T64;
+            const long row0 = t64_row0(t, tiles);
             if (row0 >= n) break;
             float4 v[4];
             t64_rows(v, AX, row0, n, rg, sg);
@@ -134,25 +117,20 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_fwd_kernel(
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) f.d[i][j] = eh_leaky(f.d[i][j], slope);
-            eh_put(Hr, rg, sg, f.d);
+                for (int j = 0; j < 4; ++j) f.d[i][j] = t64_leaky(f.d[i][j], slope);
+            t64_put0(Hr, rg, sg, f.d);
             __syncthreads();
             float o[4][4], p[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    o[i][j] = vec[EH_D + sg + 16 * j];
-                    p[i][j] = vec[2 * EH_D + sg + 16 * j];
-                }
+            t64_start1(o, vec + EH_D, sg);
+            t64_start1(p, vec + 2 * EH_D, sg);
             t64_stage_nt(Hr, LG, rg, sg, o);
             t64_stage_nt(Xr, LL, rg, sg, p);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < 4; ++i) {                                    // not t64_store1: the sum is formed in the guard
                 const long r = row0 + 4 * rg + i;
                 if (r < n) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) out_h[(size_t)r * EH_D + sg + 16 * j] = o[i][j] + eh_leaky(p[i][j], slope);
+                    for (int j = 0; j < 4; ++j) out_h[(size_t)r * EH_D + sg + 16 * j] = o[i][j] + t64_leaky(p[i][j], slope);
                 }
             }
             __syncthreads();
@@ -183,25 +161,21 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_bwd_kernel(
         const float* __restrict__ scale_h = scale ? scale + (size_t)h * n * EH_D : nullptr;
         const float* __restrict__ g_h = g + (size_t)h * n * EH_D;
         float4 ww[4], wg[4], wl[4];          // dW, dG, dL at [4 rg + i][4 sg .. + 3]
-        float csa[4], csg[4], csp[4];        // db at the columns 4 sg + j; dbg, dbl at the columns sg + 16 j
+        float cs[3][4];                      // db at the columns 4 sg + j; dbg, dbl at the columns sg + 16 j
+        t64_zero(ww), t64_zero(wg), t64_zero(wl);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ww[i] = wg[i] = wl[i] = f4_zero();
-            csa[i] = csg[i] = csp[i] = 0.f;
-        }
+        for (int j = 0; j < 4; ++j) cs[0][j] = cs[1][j] = cs[2][j] = 0.f;
         for (int t = 0; t < tiles; ++t) {
-            const long row0 = ((long)blockIdx.x * tiles + t) * T64;
+            const long row0 = t64_row0(t, tiles);
             if (row0 >= n) break;
             {
                 float4 v[4];
                 t64_rows(v, AX, row0, n, rg, sg);
                 t64_put_t(At, rg, sg, v);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(Ar + (4 * rg + i) * T64_LD + 4 * sg) = v[i];
+                t64_put0(Ar, rg, sg, v);
                 t64_rows(v, g_h, row0, n, rg, sg);
                 t64_put_t(Gt, rg, sg, v);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(Gr + (4 * rg + i) * T64_LD + 4 * sg) = v[i];
+                t64_put0(Gr, rg, sg, v);
             }
             t64_load(Xr, X, row0, n, rg, sg);
             __syncthreads();
@@ -209,7 +183,8 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_bwd_kernel(
             eh_recompute(At, LW, vec, scale_h, row0, n, rg, sg, f);
             float da[4][4];
             {
-                float4 dh[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
+                float4 dh[4];
+                t64_zero(dh);
                 t64_stage_nn(Gt, LG, rg, sg, dh);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -218,7 +193,7 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_bwd_kernel(
                     float dot = 0.f;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float lk = dv[j] * (f.d[i][j] > 0.f ? 1.f : slope);
+                        const float lk = dv[j] * t64_dleaky(f.d[i][j], slope);
                         du[j] = scale_h ? lk * f.sc[i][j] : lk;
                         dot = fmaf(f.u[i][j], du[j], dot);
                     }
@@ -227,28 +202,25 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_bwd_kernel(
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         da[i][j] = (live ? fmaf(-f.u[i][j], dot, du[j]) : du[j]) / f.nrm[i];
-                        csa[j] += da[i][j];
-                        f.d[i][j] = eh_leaky(f.d[i][j], slope);              // hh
+                        cs[0][j] += da[i][j];
+                        f.d[i][j] = t64_leaky(f.d[i][j], slope);             // hh
                     }
                 }
             }
             float dp[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dp[i][j] = vec[2 * EH_D + sg + 16 * j];
+            t64_start1(dp, vec + 2 * EH_D, sg);
             t64_stage_nt(Xr, LL, rg, sg, dp);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float gv = Gr[(4 * rg + i) * T64_LD + sg + 16 * j];
-                    dp[i][j] = gv * (dp[i][j] > 0.f ? 1.f : slope);
-                    csg[j] += gv;
-                    csp[j] += dp[i][j];
+                    dp[i][j] = gv * t64_dleaky(dp[i][j], slope);
+                    cs[1][j] += gv;
+                    cs[2][j] += dp[i][j];
                 }
             __syncthreads();                                                 // every read of AX and g transposed is done
-            eh_put(Gt, rg, sg, da);
+            t64_put0(Gt, rg, sg, da);
             t64_put(At, Pt, rg, sg, dp);
             __syncthreads();
             if (part) {
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_bwd_kernel(
             if (dX) {
                 float4 acc[4];
                 if (h) t64_rows(acc, dX, row0, n, rg, sg);
-                else acc[0] = acc[1] = acc[2] = acc[3] = f4_zero();
+                else t64_zero(acc);
                 t64_stage_nn(Pt, LL, rg, sg, acc);
                 t64_store(dX, row0, n, rg, sg, acc);
             }
@@ -271,18 +243,11 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_bwd_kernel(
                     for (int j = 0; j < 4; ++j) acc[i][j] = (h && r < n) ? dAX[(size_t)r * EH_D + sg + 16 * j] : 0.f;
                 }
                 t64_stage_nt(Gt, LW, rg, sg, acc);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const long r = row0 + 4 * rg + i;
-                    if (r < n) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) dAX[(size_t)r * EH_D + sg + 16 * j] = acc[i][j];
-                    }
-                }
+                t64_store1(dAX, row0, n, rg, sg, acc);
             }
             if (part) {
                 __syncthreads();                                             // every read of dp transposed is done
-                eh_put(Pt, rg, sg, f.d);
+                t64_put0(Pt, rg, sg, f.d);
                 __syncthreads();
                 t64_stage_nn(Gr, Pt, rg, sg, wg);
             }
@@ -290,47 +255,23 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_bwd_kernel(
         }
         if (part) {
             float* __restrict__ p = part + ((size_t)blockIdx.x * H + h) * EH_PART;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int at = (4 * rg + i) * EH_D + 4 * sg;
-                *reinterpret_cast<float4*>(p + at) = ww[i];
-                *reinterpret_cast<float4*>(p + EH_W + at) = wg[i];
-                *reinterpret_cast<float4*>(p + 2 * EH_W + at) = wl[i];
-            }
-            // the 16 row groups' column sums through LDS (the AX tile is dead): red[rg][sum][column]
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Ar[rg * EH_VEC + 4 * sg + j] = csa[j];
-                Ar[rg * EH_VEC + EH_D + sg + 16 * j] = csg[j];
-                Ar[rg * EH_VEC + 2 * EH_D + sg + 16 * j] = csp[j];
-            }
-            __syncthreads();
-            if (threadIdx.x < EH_VEC) {
-                float a = 0.f;
-                for (int q = 0; q < 16; ++q) a += Ar[q * EH_VEC + threadIdx.x];
-                p[3 * EH_W + threadIdx.x] = a;
-            }
+            t64_part_store(p, rg, sg, ww);
+            t64_part_store(p + EH_W, rg, sg, wg);
+            t64_part_store(p + 2 * EH_W, rg, sg, wl);
+            const T64Layout lay[3] = {T64_L0, T64_L1, T64_L1};
+            t64_colsum(Ar, rg, sg, lay, cs, p + 3 * EH_W);                   // through the AX tile, which is dead
         }
     }
 }
 
-// thread (quarter, output): the blocks quarter, quarter + 4, ... in order from 0, then the four quarters in order
+// t64_finish_sum over the H partials of a block, and where head h's float e goes
 __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_finish_kernel(const float* __restrict__ part, int nb, int H,
                                                                          float* __restrict__ dW, float* __restrict__ db,
                                                                          float* __restrict__ dG, float* __restrict__ dbg,
                                                                          float* __restrict__ dL, float* __restrict__ dbl) {
-    __shared__ float s[4][EH_D];
-    const int quarter = threadIdx.x / EH_D, c = threadIdx.x % EH_D;
-    const int o = blockIdx.x * EH_D + c;                       // EH_PART is a multiple of 64: o < H EH_PART
-    float a = 0.f;
-    for (int blk = quarter; blk < nb; blk += 4) a += part[(size_t)blk * H * EH_PART + o];
-    s[quarter][c] = a;
-    __syncthreads();
-    if (quarter) return;
-    a = s[0][c];
-    a += s[1][c];
-    a += s[2][c];
-    a += s[3][c];
+    int o;                                                     // EH_PART is a multiple of 64: o < H EH_PART
+    float a;
+    if (!t64_finish_sum(part, nb, (size_t)H * EH_PART, o, a)) return;
     const int h = o / EH_PART, e = o % EH_PART;
     float* dst = nullptr;
     if (e < EH_W) dst = dW ? dW + h * EH_W + e : nullptr;
@@ -342,15 +283,15 @@ __global__ __launch_bounds__(T64_BLOCK) void encoder_heads_finish_kernel(const f
     if (dst) *dst = a;
 }
 
-inline bool eh_served(int64_t n, int32_t d, int32_t H) { return d == EH_D && H >= 1 && H <= EH_MAX_HEADS && n <= EH_MAX_ROWS; }
+inline bool eh_served(int64_t n, int32_t d, int32_t H) { return d == EH_D && H >= 1 && H <= EH_MAX_HEADS && n <= T64_MAX_ROWS; }
 
 }  // namespace
 
-extern "C" int32_t mmrec_encoder_heads_rows_per_block(int64_t n) { return n < 0 || n > EH_MAX_ROWS ? 0 : eh_rows_per_block(n); }
+extern "C" int32_t mmrec_encoder_heads_rows_per_block(int64_t n) { return n < 0 || n > T64_MAX_ROWS ? 0 : t64_fuser_rows(n); }
 
 extern "C" size_t mmrec_encoder_heads_workspace_bytes(int64_t n, int32_t H) {
-    if (n < 0 || n > EH_MAX_ROWS || H < 1 || H > EH_MAX_HEADS) return 0;
-    return sizeof(float) * (size_t)eh_blocks(n) * H * EH_PART;
+    if (n < 0 || n > T64_MAX_ROWS || H < 1 || H > EH_MAX_HEADS) return 0;
+    return sizeof(float) * (size_t)t64_fuser_blocks(n) * H * EH_PART;
 }
 
 extern "C" int mmrec_encoder_heads_fwd_f32(const float* AX, const float* X, const float* W, const float* b, const float* G,
@@ -360,12 +301,10 @@ extern "C" int mmrec_encoder_heads_fwd_f32(const float* AX, const float* X, cons
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     if (!AX || !X || !W || !b || !G || !bg || !L || !bl || !out) return MMREC_ERR_BAD_ARG;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(encoder_heads_fwd_kernel), eh_lds_bytes(EH_FWD_TILES), lds_ok);
+    const int rc = t64_launch<encoder_heads_fwd_kernel>(t64_fuser_blocks(n), eh_lds_bytes(EH_FWD_TILES), mmrec_stream(stream), AX, X,
+                                                        W, b, G, bg, L, bl, scale, (long)n, t64_fuser_rows(n) / T64, (int)H, slope,
+                                                        out);
     if (rc) return rc;
-    hipLaunchKernelGGL(encoder_heads_fwd_kernel, dim3(eh_blocks(n)), dim3(T64_BLOCK), eh_lds_bytes(EH_FWD_TILES),
-                       mmrec_stream(stream), AX, X, W, b, G, bg, L, bl, scale, (long)n, eh_rows_per_block(n) / T64, (int)H, slope,
-                       out);
     MMREC_RETURN_LAUNCH_STATUS();
 }
 
@@ -379,14 +318,12 @@ extern "C" int mmrec_encoder_heads_bwd_f32(const float* AX, const float* X, cons
     const bool want_w = dW || db || dG || dbg || dL || dbl;
     if (!AX || !X || !W || !b || !G || !bg || !L || !bl || !g || (want_w && !workspace)) return MMREC_ERR_BAD_ARG;
     if (!want_w && !dAX && !dX) return 0;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(encoder_heads_bwd_kernel), eh_lds_bytes(EH_BWD_TILES), lds_ok);
-    if (rc) return rc;
     hipStream_t s = mmrec_stream(stream);
     float* part = want_w ? static_cast<float*>(workspace) : nullptr;
-    const int nb = eh_blocks(n);
-    hipLaunchKernelGGL(encoder_heads_bwd_kernel, dim3(nb), dim3(T64_BLOCK), eh_lds_bytes(EH_BWD_TILES), s, AX, X, W, b, G, bg, L, bl,
-                       scale, g, (long)n, eh_rows_per_block(n) / T64, (int)H, slope, dAX, dX, part);
+    const int nb = t64_fuser_blocks(n);
+    const int rc = t64_launch<encoder_heads_bwd_kernel>(nb, eh_lds_bytes(EH_BWD_TILES), s, AX, X, W, b, G, bg, L, bl, scale, g, (long)n,
+                                                        t64_fuser_rows(n) / T64, (int)H, slope, dAX, dX, part);
+    if (rc) return rc;
     if (want_w)
         hipLaunchKernelGGL(encoder_heads_finish_kernel, dim3(H * EH_PART / EH_D), dim3(T64_BLOCK), 0, s, part, nb, (int)H, dW, db,
                            dG, dbg, dL, dbl);

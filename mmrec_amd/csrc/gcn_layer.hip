@@ -5,10 +5,9 @@
 // Per row (Wc [64][64] as [in][out]; Wl [64][64] and Wg = [Gh | Gx] [64][128] as torch's [out][in]; R the id embedding or NULL):
 //     a = AX Wc, h = leaky(a);   p = X Wl^T + bl, xh = leaky(p) + R;   q = h Gh^T + xh Gx^T + bg;   out = leaky(q)
 //
-// THE PLAN (what the fuzz's error bound counts).  One 256-thread workgroup per block of R = mmrec_gcn_layer_rows_per_block(n)
-// consecutive rows, walked as R / 64 tiles of 64 rows.  Thread (rg, sg) of 16 x 16 owns the rows 4 rg .. + 3.
-//   stage   a 64-term fma chain per output, the summed index ascending, onto a given start (tile64.h): 64 roundings.
-//           a: over the input column from 0;  p: from bl;  q: over h's column from bg and ON, over xh's column: 128 roundings.
+// THE PLAN (what the fuzz's error bound counts) is tile64.h's: blocks of R = mmrec_gcn_layer_rows_per_block(n) rows, stage,
+// weight partials, column sums, finish.  This op's own:
+//   stage   a: over the input column from 0;  p: from bl;  q: over h's column from bg and ON, over xh's column: 128 roundings.
 //   leaky(z) = z > 0 ? z : slope * z;  xh = leaky(p) + R is one addition (R NULL: none).
 // Backward from g [n, 64] and the saved out, a, h, p, xh RECOMPUTED as above; dq = g * (out > 0 ? 1 : slope): the sign of out is
 // the sign of q.  The PHASE LOOP IS OUTERMOST inside the workgroup, as the head loop of encoder_heads.hip: two matrices in LDS,
@@ -19,10 +18,7 @@
 //   skip    Wl, Gx:  dxh = the stage of dq Gx over the output column from 0 = dR;  dp = dxh * (p > 0 ? 1 : slope);
 //           dX = the stage of dp Wl over the output column from 0;  dWl[o][k] alike (dp^T X), dGx[o][k] alike (dq^T xh);
 //           dbl: the column sums of dp.
-//   The column sums: a thread adds its four rows in order, tile after tile, from 0; then the 16 row groups are added in order from 0.
-//   Finish: thread (quarter, output) adds the blocks quarter, quarter + 4, ... in order from 0, then the four quarters in order.
-// NO ATOMICS, every order fixed by n alone.  Rows past n are zero in every tile of AX, X, g (so dq, and every term they add to a
-// sum, is an exact zero) and are never stored.
+// Rows past n are zero in every tile of AX, X, g (so dq, and every term they add to a sum, is an exact zero).
 // Workspace: per block 4 (64 64) + 2 (64) = 16,512 floats: [dWc][dGh][dWl][dGx][dbg][dbl].
 // LDS: forward 4 matrices + 4 tiles, backward 2 matrices + 6 tiles of 17,408 B, + 512 B of biases: 139,776 B both.
 #include "tile64.h"
@@ -30,28 +26,21 @@
 namespace {
 
 constexpr int GL_D = 64;
-constexpr int GL_MAX_BLOCKS = 256;
 constexpr int GL_W = GL_D * GL_D;
 constexpr int GL_PART = 4 * GL_W + 2 * GL_D;                // floats of one block's partial
 constexpr int GL_VEC = 2 * GL_D;                            // bl, bg in LDS
 constexpr int GL_IMAGES = 8;                                // matrices + tiles, forward and backward alike
-constexpr int64_t GL_MAX_ROWS = (int64_t)1 << 30;
 constexpr size_t GL_LDS = sizeof(float) * ((size_t)GL_IMAGES * T64_FLOATS + GL_VEC);
 
-inline int gl_rows_per_block(int64_t n) { return t64_rows_per_block(n, GL_MAX_BLOCKS); }
-inline int gl_blocks(int64_t n) { return t64_blocks(n, GL_MAX_BLOCKS); }
-
-__device__ __forceinline__ float gl_leaky(float z, float slope) { return z > 0.f ? z : slope * z; }
-__device__ __forceinline__ float gl_dleaky(float z, float slope) { return z > 0.f ? 1.f : slope; }
-
-// layout L0 registers (rows 4 rg + i, columns 4 sg .. + 3) to a row-major tile
-__device__ __forceinline__ void gl_put(float* __restrict__ T, int rg, int sg, const float4 (&v)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(T + (4 * rg + i) * T64_LD + 4 * sg) = v[i];
-}
-
 __device__ __forceinline__ float4 gl_leaky4(const float4 z, float slope) {
-    return make_float4(gl_leaky(z.x, slope), gl_leaky(z.y, slope), gl_leaky(z.z, slope), gl_leaky(z.w, slope));
+    return make_float4(t64_leaky(z.x, slope), t64_leaky(z.y, slope), t64_leaky(z.z, slope), t64_leaky(z.w, slope));
+}
+// dz = dy * (z > 0 ? 1 : slope)
+__device__ __forceinline__ void gl_dleaky4(float4& dy, const float4 z, float slope) {
+    dy.x *= t64_dleaky(z.x, slope);
+    dy.y *= t64_dleaky(z.y, slope);
+    dy.z *= t64_dleaky(z.z, slope);
+    dy.w *= t64_dleaky(z.w, slope);
 }
 
 // dq of the thread's rows in layout L0: g * (out > 0 ? 1 : slope); rows past n are zeros
@@ -61,29 +50,22 @@ __device__ __forceinline__ void gl_dq(float4 (&dq)[4], const float* __restrict__
     t64_rows(dq, g, row0, n, rg, sg);
     t64_rows(o, out, row0, n, rg, sg);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        dq[i].x *= gl_dleaky(o[i].x, slope);
-        dq[i].y *= gl_dleaky(o[i].y, slope);
-        dq[i].z *= gl_dleaky(o[i].z, slope);
-        dq[i].w *= gl_dleaky(o[i].w, slope);
-    }
+    for (int i = 0; i < 4; ++i) gl_dleaky4(dq[i], o[i], slope);
 }
 
-// p (layout L1: rows 4 rg + i, columns sg + 16 j) from the X tile, and xh = leaky(p) + R
+// p (layout L1: rows 4 rg + i, columns sg + 16 j) from the X tile, and xh = leaky(p) + R.  A row past n gets NO addition:
+// adding a zero in R's place would turn a -0 into +0
 __device__ __forceinline__ void gl_skip(const float* __restrict__ Xr, const float* __restrict__ LWl, const float* __restrict__ vec,
                                         const float* __restrict__ R, long row0, long n, int rg, int sg, float slope,
                                         float (&p)[4][4], float (&xh)[4][4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) p[i][j] = vec[sg + 16 * j];
+    t64_start1(p, vec, sg);
     t64_stage_nt(Xr, LWl, rg, sg, p);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const long r = row0 + 4 * rg + i;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            xh[i][j] = gl_leaky(p[i][j], slope);
+            xh[i][j] = t64_leaky(p[i][j], slope);
             if (R && r < n) xh[i][j] += R[(size_t)r * GL_D + sg + 16 * j];
         }
     }
@@ -110,7 +92,7 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_fwd_kernel(
     t64_matrix_ld(LGx, Wg + GL_D, 2 * GL_D);
     if (threadIdx.x < GL_VEC) vec[threadIdx.x] = threadIdx.x < GL_D ? bl[threadIdx.x] : bg[threadIdx.x - GL_D];
     for (int t = 0; t < tiles; ++t) {
-        const long row0 = ((long)blockIdx.x * tiles + t) * T64;
+        const long row0 = t64_row0(t, tiles);
         if (row0 >= n) break;
         {
             float4 v[4];
@@ -120,11 +102,12 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_fwd_kernel(
         t64_load(Xr, X, row0, n, rg, sg);
         __syncthreads();
         {
-            float4 a[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
+            float4 a[4];
+            t64_zero(a);
             t64_stage_nn(At, LWc, rg, sg, a);
 #pragma unroll
             for (int i = 0; i < 4; ++i) a[i] = gl_leaky4(a[i], slope);
-            gl_put(Hr, rg, sg, a);
+            t64_put0(Hr, rg, sg, a);
             float p[4][4], xh[4][4];
             gl_skip(Xr, LWl, vec, R, row0, n, rg, sg, slope, p, xh);
             t64_put(XHr, nullptr, rg, sg, xh);
@@ -132,33 +115,20 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_fwd_kernel(
         __syncthreads();
         float q[4][4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)                                          // not t64_start1: 2 more VGPRs, 0.5 % slower
 #pragma unroll
             for (int j = 0; j < 4; ++j) q[i][j] = vec[GL_D + sg + 16 * j];
         t64_stage_nt(Hr, LGh, rg, sg, q);
         t64_stage_nt(XHr, LGx, rg, sg, q);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i) {                                        // not t64_store1: leaky is applied in the guard
             const long r = row0 + 4 * rg + i;
             if (r < n) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) out[(size_t)r * GL_D + sg + 16 * j] = gl_leaky(q[i][j], slope);
+                for (int j = 0; j < 4; ++j) out[(size_t)r * GL_D + sg + 16 * j] = t64_leaky(q[i][j], slope);
             }
         }
         __syncthreads();
-    }
-}
-
-// the 16 row groups' column sums through a dead tile, then thread c < 64 adds them in order into dst[c]
-__device__ __forceinline__ void gl_colsum(float* __restrict__ red, int rg, const int (&col)[4], const float (&cs)[4],
-                                          float* __restrict__ dst) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[rg * GL_D + col[j]] = cs[j];
-    __syncthreads();
-    if (threadIdx.x < GL_D) {
-        float a = 0.f;
-        for (int q = 0; q < 16; ++q) a += red[q * GL_D + threadIdx.x];
-        dst[threadIdx.x] = a;
     }
 }
 
@@ -190,44 +160,40 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_bwd_kernel(
         t64_matrix(M0, Wc);
         t64_matrix_ld(M1, Wg, 2 * GL_D);
         float4 ww[4], wg[4];                             // dWc, dGh at [4 rg + i][4 sg .. + 3]
-        float cs[4] = {0.f, 0.f, 0.f, 0.f};              // dbg at the columns 4 sg + j
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ww[i] = wg[i] = f4_zero();
+        float cs[1][4] = {{0.f, 0.f, 0.f, 0.f}};         // dbg at the columns 4 sg + j
+        t64_zero(ww), t64_zero(wg);
         for (int t = 0; t < tiles; ++t) {
-            const long row0 = ((long)blockIdx.x * tiles + t) * T64;
+            const long row0 = t64_row0(t, tiles);
             if (row0 >= n) break;
             {
                 float4 v[4];
                 t64_rows(v, AX, row0, n, rg, sg);
                 t64_put_t(At, rg, sg, v);
-                gl_put(Ar, rg, sg, v);
+                t64_put0(Ar, rg, sg, v);
                 gl_dq(v, g, out, row0, n, rg, sg, slope);
                 t64_put_t(Qt, rg, sg, v);
-                gl_put(Qr, rg, sg, v);
+                t64_put0(Qr, rg, sg, v);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    cs[0] += v[i].x;
-                    cs[1] += v[i].y;
-                    cs[2] += v[i].z;
-                    cs[3] += v[i].w;
+                    cs[0][0] += v[i].x;
+                    cs[0][1] += v[i].y;
+                    cs[0][2] += v[i].z;
+                    cs[0][3] += v[i].w;
                 }
             }
             __syncthreads();
             {
-                float4 a[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
-                float4 dh[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
+                float4 a[4], dh[4];
+                t64_zero(a), t64_zero(dh);
                 t64_stage_nn(At, M0, rg, sg, a);
                 t64_stage_nn(Qt, M1, rg, sg, dh);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    dh[i].x *= gl_dleaky(a[i].x, slope);
-                    dh[i].y *= gl_dleaky(a[i].y, slope);
-                    dh[i].z *= gl_dleaky(a[i].z, slope);
-                    dh[i].w *= gl_dleaky(a[i].w, slope);
+                    gl_dleaky4(dh[i], a[i], slope);      // da
                     a[i] = gl_leaky4(a[i], slope);
                 }
-                gl_put(Dr, rg, sg, dh);
-                gl_put(Hr, rg, sg, a);
+                t64_put0(Dr, rg, sg, dh);
+                t64_put0(Hr, rg, sg, a);
             }
             __syncthreads();
             if (part) {
@@ -236,31 +202,17 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_bwd_kernel(
             }
             if (dAX) {
                 float acc[4][4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+                t64_zero(acc);
                 t64_stage_nt(Dr, M0, rg, sg, acc);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const long r = row0 + 4 * rg + i;
-                    if (r < n) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) dAX[(size_t)r * GL_D + sg + 16 * j] = acc[i][j];
-                    }
-                }
+                t64_store1(dAX, row0, n, rg, sg, acc);
             }
             __syncthreads();
         }
         if (part) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int at = (4 * rg + i) * GL_D + 4 * sg;
-                *reinterpret_cast<float4*>(mine + at) = ww[i];
-                *reinterpret_cast<float4*>(mine + GL_W + at) = wg[i];
-            }
-            const int col[4] = {4 * sg, 4 * sg + 1, 4 * sg + 2, 4 * sg + 3};
-            gl_colsum(Ar, rg, col, cs, mine + 4 * GL_W);
+            t64_part_store(mine, rg, sg, ww);
+            t64_part_store(mine + GL_W, rg, sg, wg);
+            const T64Layout lay[1] = {T64_L0};
+            t64_colsum(Ar, rg, sg, lay, cs, mine + 4 * GL_W);
         }
         __syncthreads();                                 // every read of the phase's matrices and column sums is done
     }
@@ -275,35 +227,31 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_bwd_kernel(
         t64_matrix_ld_t(M1, Wg + GL_D, 2 * GL_D);
         if (threadIdx.x < GL_D) vec[threadIdx.x] = bl[threadIdx.x];
         float4 wl[4], wx[4];                             // dWl, dGx at [4 rg + i][4 sg .. + 3]
-        float cs[4] = {0.f, 0.f, 0.f, 0.f};              // dbl at the columns sg + 16 j
-#pragma unroll
-        for (int i = 0; i < 4; ++i) wl[i] = wx[i] = f4_zero();
+        float cs[1][4] = {{0.f, 0.f, 0.f, 0.f}};         // dbl at the columns sg + 16 j
+        t64_zero(wl), t64_zero(wx);
         for (int t = 0; t < tiles; ++t) {
-            const long row0 = ((long)blockIdx.x * tiles + t) * T64;
+            const long row0 = t64_row0(t, tiles);
             if (row0 >= n) break;
             t64_load(Xr, X, row0, n, rg, sg);
             {
                 float4 v[4];
                 gl_dq(v, g, out, row0, n, rg, sg, slope);
-                gl_put(Qr, rg, sg, v);
+                t64_put0(Qr, rg, sg, v);
             }
             __syncthreads();
             {
                 float p[4][4], xh[4][4], dxh[4][4];
                 gl_skip(Xr, M0, vec, R, row0, n, rg, sg, slope, p, xh);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) dxh[i][j] = 0.f;
+                t64_zero(dxh);
                 t64_stage_nt(Qr, M1, rg, sg, dxh);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const long r = row0 + 4 * rg + i;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
+                    for (int j = 0; j < 4; ++j) {                            // dR not through t64_store1: 32 more VGPRs
                         if (dR && r < n) dR[(size_t)r * GL_D + sg + 16 * j] = dxh[i][j];
-                        dxh[i][j] *= gl_dleaky(p[i][j], slope);               // dp
-                        cs[j] += dxh[i][j];
+                        dxh[i][j] *= t64_dleaky(p[i][j], slope);             // dp
+                        cs[0][j] += dxh[i][j];
                     }
                 }
                 t64_put(Pr, Pt, rg, sg, dxh);
@@ -315,42 +263,30 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_bwd_kernel(
                 t64_stage_nn(Qr, XHr, rg, sg, wx);
             }
             if (dX) {
-                float4 acc[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
+                float4 acc[4];
+                t64_zero(acc);
                 t64_stage_nn(Pt, M0, rg, sg, acc);
                 t64_store(dX, row0, n, rg, sg, acc);
             }
             __syncthreads();
         }
         if (part) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int at = (4 * rg + i) * GL_D + 4 * sg;
-                *reinterpret_cast<float4*>(mine + 2 * GL_W + at) = wl[i];
-                *reinterpret_cast<float4*>(mine + 3 * GL_W + at) = wx[i];
-            }
-            const int col[4] = {sg, sg + 16, sg + 32, sg + 48};
-            gl_colsum(Xr, rg, col, cs, mine + 4 * GL_W + GL_D);
+            t64_part_store(mine + 2 * GL_W, rg, sg, wl);
+            t64_part_store(mine + 3 * GL_W, rg, sg, wx);
+            const T64Layout lay[1] = {T64_L1};
+            t64_colsum(Xr, rg, sg, lay, cs, mine + 4 * GL_W + GL_D);
         }
     }
 }
 
-// thread (quarter, output): the blocks quarter, quarter + 4, ... in order from 0, then the four quarters in order
+// t64_finish_sum, and where a partial's float e goes
 __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_finish_kernel(const float* __restrict__ part, int nb, float* __restrict__ dWc,
                                                                      float* __restrict__ dWl, float* __restrict__ dbl,
                                                                      float* __restrict__ dWg, float* __restrict__ dbg) {
-    __shared__ float s[4][GL_D];
-    const int quarter = threadIdx.x / GL_D, c = threadIdx.x % GL_D;
-    const int e = blockIdx.x * GL_D + c;                       // GL_PART is a multiple of 64: e < GL_PART
-    float a = 0.f;
-    for (int blk = quarter; blk < nb; blk += 4) a += part[(size_t)blk * GL_PART + e];
-    s[quarter][c] = a;
-    __syncthreads();
-    if (quarter) return;
-    a = s[0][c];
-    a += s[1][c];
-    a += s[2][c];
-    a += s[3][c];
-    const int row = (e % GL_W) / GL_D;                         // of a matrix partial: blockIdx.x % 64, the column is c
+    int e;                                                     // GL_PART is a multiple of 64: e < GL_PART
+    float a;
+    if (!t64_finish_sum(part, nb, GL_PART, e, a)) return;
+    const int row = (e % GL_W) / GL_D, c = e % GL_D;           // of a matrix partial
     float* dst = nullptr;
     if (e < GL_W) dst = dWc ? dWc + e : nullptr;
     else if (e < 2 * GL_W) dst = dWg ? dWg + row * 2 * GL_D + c : nullptr;
@@ -361,15 +297,15 @@ __global__ __launch_bounds__(T64_BLOCK) void gcn_layer_finish_kernel(const float
     if (dst) *dst = a;
 }
 
-inline bool gl_served(int64_t n, int32_t d, float slope) { return d == GL_D && slope > 0.f && n <= GL_MAX_ROWS; }
+inline bool gl_served(int64_t n, int32_t d, float slope) { return d == GL_D && slope > 0.f && n <= T64_MAX_ROWS; }
 
 }  // namespace
 
-extern "C" int32_t mmrec_gcn_layer_rows_per_block(int64_t n) { return n < 0 || n > GL_MAX_ROWS ? 0 : gl_rows_per_block(n); }
+extern "C" int32_t mmrec_gcn_layer_rows_per_block(int64_t n) { return n < 0 || n > T64_MAX_ROWS ? 0 : t64_fuser_rows(n); }
 
 extern "C" size_t mmrec_gcn_layer_workspace_bytes(int64_t n) {
-    if (n < 0 || n > GL_MAX_ROWS) return 0;
-    return sizeof(float) * (size_t)gl_blocks(n) * GL_PART;
+    if (n < 0 || n > T64_MAX_ROWS) return 0;
+    return sizeof(float) * (size_t)t64_fuser_blocks(n) * GL_PART;
 }
 
 extern "C" int mmrec_gcn_layer_fwd_f32(const float* AX, const float* X, const float* R, const float* Wc, const float* Wl,
@@ -379,11 +315,9 @@ extern "C" int mmrec_gcn_layer_fwd_f32(const float* AX, const float* X, const fl
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     if (!AX || !X || !Wc || !Wl || !bl || !Wg || !bg || !out) return MMREC_ERR_BAD_ARG;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(gcn_layer_fwd_kernel), GL_LDS, lds_ok);
+    const int rc = t64_launch<gcn_layer_fwd_kernel>(t64_fuser_blocks(n), GL_LDS, mmrec_stream(stream), AX, X, R, Wc, Wl, bl, Wg, bg,
+                                                    (long)n, t64_fuser_rows(n) / T64, slope, out);
     if (rc) return rc;
-    hipLaunchKernelGGL(gcn_layer_fwd_kernel, dim3(gl_blocks(n)), dim3(T64_BLOCK), GL_LDS, mmrec_stream(stream), AX, X, R, Wc, Wl, bl,
-                       Wg, bg, (long)n, gl_rows_per_block(n) / T64, slope, out);
     MMREC_RETURN_LAUNCH_STATUS();
 }
 
@@ -397,14 +331,12 @@ extern "C" int mmrec_gcn_layer_bwd_f32(const float* AX, const float* X, const fl
     const bool want_w = dWc || dWl || dbl || dWg || dbg;
     if (!AX || !X || !Wc || !Wl || !bl || !Wg || !bg || !out || !g || (want_w && !workspace)) return MMREC_ERR_BAD_ARG;
     if (!want_w && !dAX && !dX && !dR) return 0;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(gcn_layer_bwd_kernel), GL_LDS, lds_ok);
-    if (rc) return rc;
     hipStream_t s = mmrec_stream(stream);
     float* part = want_w ? static_cast<float*>(workspace) : nullptr;
-    const int nb = gl_blocks(n);
-    hipLaunchKernelGGL(gcn_layer_bwd_kernel, dim3(nb), dim3(T64_BLOCK), GL_LDS, s, AX, X, R, Wc, Wl, bl, Wg, out, g, (long)n,
-                       gl_rows_per_block(n) / T64, slope, dAX, dX, dR, part);
+    const int nb = t64_fuser_blocks(n);
+    const int rc = t64_launch<gcn_layer_bwd_kernel>(nb, GL_LDS, s, AX, X, R, Wc, Wl, bl, Wg, out, g, (long)n, t64_fuser_rows(n) / T64,
+                                                    slope, dAX, dX, dR, part);
+    if (rc) return rc;
     if (want_w)
         hipLaunchKernelGGL(gcn_layer_finish_kernel, dim3(GL_PART / GL_D), dim3(T64_BLOCK), 0, s, part, nb, dWc, dWl, dbl, dWg, dbg);
     MMREC_RETURN_LAUNCH_STATUS();

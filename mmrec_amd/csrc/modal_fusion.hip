@@ -6,11 +6,10 @@
 //     zV = V Wq^T + bq, hV = tanh(zV), sV = <hV, q>   (zT, hT, sT alike)      (aV, aT) = softmax(sV, sT)      m = aV V + aT T
 //     pV = sigmoid(C Wv^T + bv), pT = sigmoid(C Wt^T + bt)       side = (pV (V - m) + pT (T - m) + m) / 3       out = C + side
 //
-// THE PLAN (what the fuzz's error bound counts).  One 256-thread workgroup per block of R = mmrec_modal_fusion_rows_per_block(n)
-// consecutive rows, walked as R / 64 tiles of 64 rows; Wq, Wv, Wt stay in LDS for the block's life, as they lie in memory
-// ([out][in], 68-float rows).  Thread (rg, sg) of 16 x 16 owns the rows 4 rg .. + 3.
-//   stage   a 64-term fma chain per output, the summed index ascending, onto a given start (tile64.h): 64 roundings.
-//           z / u: the chain over the input column k starts at the bias.
+// THE PLAN (what the fuzz's error bound counts) is tile64.h's: blocks of R = mmrec_modal_fusion_rows_per_block(n) rows, stage,
+// weight partials, column sums, finish.  Wq, Wv, Wt stay in LDS for the block's life, as they lie in memory ([out][in], 68-float
+// rows).  This op's own:
+//   stage   z / u: the chain over the input column k starts at the bias.
 //   tanh    q = expf(-2 |z|), h = copysign((1 - q) / (1 + q), z);  sigmoid: q = expf(-|z|), p = (z >= 0 ? 1 : q) / (1 + q).
 //           Exactly +-1 and 1 / 0 once q underflows to 0; the argument of expf is exact and never positive.
 //   score   the thread's columns c = sg, sg + 16, sg + 32, sg + 48: s = fma(h_c, q_c, s) from 0 in this order, then the butterfly
@@ -24,34 +23,24 @@
 //   dV = the stage over the output column o of dzV Wq, started at fma(aV, dm, G3 pV);  dT alike;
 //   dC = the stage of duV Wv started at g_out (or 0), continued by the stage of duT Wt.
 //   dWq[o][k] = one fma chain over the block's rows: per tile the 64 rows of dzV^T V, then the 64 of dzT^T T;  dWv, dWt: duV^T C,
-//   duT^T C.   The column sums dbq (terms dzV + dzT), dbv (duV), dbt (duT), dq (fma(dsT, hT, dsV hV)): a thread adds its four rows
-//   in order, tile after tile; then the 16 row groups are added in order from 0.
-//   Finish: thread (quarter, output) adds the blocks quarter, quarter + 4, ... in order from 0, then the four quarters in order.
-// NO ATOMICS, every order fixed by n alone.  Rows past n are zero in every tile (and get G = 0) and are never stored.
+//   duT^T C.   The column sums: dbq (terms dzV + dzT), dbv (duV), dbt (duT), dq (fma(dsT, hT, dsV hV)).
+// Rows past n get G = 0.
 // Workspace: 3 (64 64 + 64) + 64 = 12,544 floats per block: [dWq][dWv][dWt][dbq][dbv][dbt][dq].
 #include "tile64.h"
 
 namespace {
 
 constexpr int MF_D = 64;
-constexpr int MF_MAX_BLOCKS = 256;
-constexpr int MF_PART = 3 * (MF_D * MF_D + MF_D) + MF_D;    // floats of one block's partial
+constexpr int MF_W = MF_D * MF_D;
+constexpr int MF_PART = 3 * (MF_W + MF_D) + MF_D;           // floats of one block's partial
 constexpr int MF_VEC = 4 * MF_D;                            // bq, q, bv, bt in LDS
 constexpr int MF_FWD_TILES = 3, MF_BWD_TILES = 5;
-constexpr int64_t MF_MAX_ROWS = (int64_t)1 << 30;
 
 constexpr size_t mf_lds_bytes(int tiles) { return sizeof(float) * ((size_t)(3 + tiles) * T64_FLOATS + MF_VEC); }
-
-inline int mf_rows_per_block(int64_t n) { return t64_rows_per_block(n, MF_MAX_BLOCKS); }
-inline int mf_blocks(int64_t n) { return t64_blocks(n, MF_MAX_BLOCKS); }
 
 __device__ __forceinline__ float mf_tanh(float z) {
     const float q = expf(-2.f * fabsf(z));
     return copysignf((1.f - q) / (1.f + q), z);
-}
-__device__ __forceinline__ float mf_sigmoid(float z) {
-    const float q = expf(-fabsf(z));
-    return (z >= 0.f ? 1.f : q) / (1.f + q);
 }
 
 __device__ __forceinline__ void mf_setup(float* __restrict__ LWq, float* __restrict__ LWv, float* __restrict__ LWt,
@@ -81,10 +70,7 @@ __device__ __forceinline__ void mf_recompute(const float* __restrict__ Vr, const
     for (int pass = 0; pass < 2; ++pass) {
         float (&h)[4][4] = pass ? f.hT : f.hV;
         float (&s)[4] = pass ? sT : sV;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) h[i][j] = vec[sg + 16 * j];
+        t64_start1(h, vec, sg);
         t64_stage_nt(pass ? Tr : Vr, LWq, rg, sg, h);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -108,15 +94,12 @@ __device__ __forceinline__ void mf_recompute(const float* __restrict__ Vr, const
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         float (&p)[4][4] = pass ? f.pT : f.pV;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[i][j] = vec[(pass ? 3 : 2) * MF_D + sg + 16 * j];
+        t64_start1(p, vec + (pass ? 3 : 2) * MF_D, sg);
         t64_stage_nt(Cr, pass ? LWt : LWv, rg, sg, p);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) p[i][j] = mf_sigmoid(p[i][j]);
+            for (int j = 0; j < 4; ++j) p[i][j] = stable_sigmoid(p[i][j]);
     }
 }
 
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_fwd_kernel(
     const int rg = threadIdx.x / 16, sg = threadIdx.x % 16;
     mf_setup(LWq, LWv, LWt, vec, Wq, bq, q, Wv, bv, Wt, bt);
     for (int t = 0; t < tiles; ++t) {
-        const long row0 = ((long)blockIdx.x * tiles + t) * T64;
+        const long row0 = t64_row0(t, tiles);
         if (row0 >= n) break;
         t64_load(Vr, V, row0, n, rg, sg);
         t64_load(Tr, T, row0, n, rg, sg);
@@ -144,21 +127,19 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_fwd_kernel(
         __syncthreads();
         MfRows f;
         mf_recompute(Vr, Tr, Cr, LWq, LWv, LWt, vec, rg, sg, f);
+        float s[4][4], o[4][4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const long r = row0 + 4 * rg + i;
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int c = sg + 16 * j, at = (4 * rg + i) * T64_LD + c;
+                const int at = (4 * rg + i) * T64_LD + sg + 16 * j;
                 const float v = Vr[at], x = Tr[at];
                 const float m = fmaf(f.aT[i], x, f.aV[i] * v);
-                const float s = fmaf(f.pT[i][j], x - m, fmaf(f.pV[i][j], v - m, m)) / 3.f;
-                if (r < n) {
-                    side[(size_t)r * MF_D + c] = s;
-                    out[(size_t)r * MF_D + c] = Cr[at] + s;
-                }
+                s[i][j] = fmaf(f.pT[i][j], x - m, fmaf(f.pV[i][j], v - m, m)) / 3.f;
+                o[i][j] = Cr[at] + s[i][j];
             }
-        }
+        t64_store1(side, row0, n, rg, sg, s);
+        t64_store1(out, row0, n, rg, sg, o);
         __syncthreads();
     }
 }
@@ -182,15 +163,10 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_bwd_kernel(
     const int rg = threadIdx.x / 16, sg = threadIdx.x % 16;
     float4 wq[4], wv[4], wt[4];              // dWq, dWv, dWt at [4 rg + i][4 sg .. + 3]
     float cs[4][4];                          // the column sums dbq, dbv, dbt, dq at the columns sg + 16 j
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wq[i] = wv[i] = wt[i] = f4_zero();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cs[i][j] = 0.f;
-    }
+    t64_zero(wq), t64_zero(wv), t64_zero(wt), t64_zero(cs);
     mf_setup(LWq, LWv, LWt, vec, Wq, bq, q, Wv, bv, Wt, bt);
     for (int t = 0; t < tiles; ++t) {
-        const long row0 = ((long)blockIdx.x * tiles + t) * T64;
+        const long row0 = t64_row0(t, tiles);
         if (row0 >= n) break;
         t64_load(Vr, V, row0, n, rg, sg);
         t64_load(Tr, T, row0, n, rg, sg);
@@ -201,8 +177,7 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_bwd_kernel(
         MfRows f;
         mf_recompute(Vr, Tr, Cr, LWq, LWv, LWt, vec, rg, sg, f);
         float4 dc[4];                        // dC starts at g_out
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dc[i] = *reinterpret_cast<const float4*>(Xt + (4 * rg + i) * T64_LD + 4 * sg);
+        t64_get0(dc, Xt, rg, sg);
         float duV[4][4], duT[4][4], sV_[4][4], sT_[4][4];      // sV_, sT_: the starts of dV and dT
         float dsV[4];
 #pragma unroll
@@ -260,8 +235,7 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_bwd_kernel(
         __syncthreads();
         if (part) t64_stage_nn(Xr, Vr, rg, sg, wq);
         if (dV) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dc[i] = *reinterpret_cast<const float4*>(Cr + (4 * rg + i) * T64_LD + 4 * sg);
+            t64_get0(dc, Cr, rg, sg);
             t64_stage_nn(Xt, LWq, rg, sg, dc);
             t64_store(dV, row0, n, rg, sg, dc);
         }
@@ -271,8 +245,7 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_bwd_kernel(
         __syncthreads();
         if (part) t64_stage_nn(Xr, Tr, rg, sg, wq);
         if (dT) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dc[i] = *reinterpret_cast<const float4*>(Cr + (4 * rg + i) * T64_LD + 4 * sg);
+            t64_get0(dc, Cr, rg, sg);
             t64_stage_nn(Xt, LWq, rg, sg, dc);
             t64_store(dT, row0, n, rg, sg, dc);
         }
@@ -280,44 +253,24 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_bwd_kernel(
     }
     if (part) {
         float* __restrict__ p = part + (size_t)blockIdx.x * MF_PART;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int at = (4 * rg + i) * MF_D + 4 * sg;
-            *reinterpret_cast<float4*>(p + at) = wq[i];
-            *reinterpret_cast<float4*>(p + MF_D * MF_D + at) = wv[i];
-            *reinterpret_cast<float4*>(p + 2 * MF_D * MF_D + at) = wt[i];
-        }
-        // the 16 row groups' column sums through LDS (the V tile is dead): red[rg][sum][column]
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) Vr[rg * 4 * MF_D + k * MF_D + sg + 16 * j] = cs[k][j];
-        __syncthreads();
-        float a = 0.f;
-        for (int g = 0; g < 16; ++g) a += Vr[g * 4 * MF_D + threadIdx.x];
-        p[3 * MF_D * MF_D + threadIdx.x] = a;
+        t64_part_store(p, rg, sg, wq);
+        t64_part_store(p + MF_W, rg, sg, wv);
+        t64_part_store(p + 2 * MF_W, rg, sg, wt);
+        const T64Layout lay[4] = {T64_L1, T64_L1, T64_L1, T64_L1};
+        t64_colsum(Vr, rg, sg, lay, cs, p + 3 * MF_W);      // through the V tile, which is dead
     }
 }
 
-// thread (quarter, output): the blocks quarter, quarter + 4, ... in order from 0, then the four quarters in order
+// t64_finish_sum, and where a partial's float o goes
 __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_finish_kernel(const float* __restrict__ part, int nb,
                                                                         float* __restrict__ dWq, float* __restrict__ dbq,
                                                                         float* __restrict__ dq, float* __restrict__ dWv,
                                                                         float* __restrict__ dbv, float* __restrict__ dWt,
                                                                         float* __restrict__ dbt) {
-    __shared__ float s[4][MF_D];
-    const int quarter = threadIdx.x / MF_D, c = threadIdx.x % MF_D;
-    const int o = blockIdx.x * MF_D + c;                       // MF_PART is a multiple of 64: o < MF_PART
-    float a = 0.f;
-    for (int b = quarter; b < nb; b += 4) a += part[(size_t)b * MF_PART + o];
-    s[quarter][c] = a;
-    __syncthreads();
-    if (quarter) return;
-    a = s[0][c];
-    a += s[1][c];
-    a += s[2][c];
-    a += s[3][c];
-    constexpr int W = MF_D * MF_D;
+    int o;                                                     // MF_PART is a multiple of 64: o < MF_PART
+    float a;
+    if (!t64_finish_sum(part, nb, MF_PART, o, a)) return;
+    constexpr int W = MF_W;
     float* dst = nullptr;
     if (o < W) dst = dWq ? dWq + o : nullptr;
     else if (o < 2 * W) dst = dWv ? dWv + (o - W) : nullptr;
@@ -331,25 +284,23 @@ __global__ __launch_bounds__(T64_BLOCK) void modal_fusion_finish_kernel(const fl
 
 }  // namespace
 
-extern "C" int32_t mmrec_modal_fusion_rows_per_block(int64_t n) { return n < 0 || n > MF_MAX_ROWS ? 0 : mf_rows_per_block(n); }
+extern "C" int32_t mmrec_modal_fusion_rows_per_block(int64_t n) { return n < 0 || n > T64_MAX_ROWS ? 0 : t64_fuser_rows(n); }
 
 extern "C" size_t mmrec_modal_fusion_workspace_bytes(int64_t n) {
-    if (n < 0 || n > MF_MAX_ROWS) return 0;
-    return sizeof(float) * (size_t)mf_blocks(n) * MF_PART;
+    if (n < 0 || n > T64_MAX_ROWS) return 0;
+    return sizeof(float) * (size_t)t64_fuser_blocks(n) * MF_PART;
 }
 
 extern "C" int mmrec_modal_fusion_fwd_f32(const float* V, const float* T, const float* C, const float* Wq, const float* bq,
                                           const float* q, const float* Wv, const float* bv, const float* Wt, const float* bt,
                                           int64_t n, int32_t d, float* side, float* out, mmrec_stream_t stream) {
-    if (d != MF_D || n > MF_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
+    if (d != MF_D || n > T64_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     if (!V || !T || !C || !Wq || !bq || !q || !Wv || !bv || !Wt || !bt || !side || !out) return MMREC_ERR_BAD_ARG;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(modal_fusion_fwd_kernel), mf_lds_bytes(MF_FWD_TILES), lds_ok);
+    const int rc = t64_launch<modal_fusion_fwd_kernel>(t64_fuser_blocks(n), mf_lds_bytes(MF_FWD_TILES), mmrec_stream(stream), V, T,
+                                                       C, Wq, bq, q, Wv, bv, Wt, bt, (long)n, t64_fuser_rows(n) / T64, side, out);
     if (rc) return rc;
-    hipLaunchKernelGGL(modal_fusion_fwd_kernel, dim3(mf_blocks(n)), dim3(T64_BLOCK), mf_lds_bytes(MF_FWD_TILES),
-                       mmrec_stream(stream), V, T, C, Wq, bq, q, Wv, bv, Wt, bt, (long)n, mf_rows_per_block(n) / T64, side, out);
     MMREC_RETURN_LAUNCH_STATUS();
 }
 
@@ -358,20 +309,18 @@ extern "C" int mmrec_modal_fusion_bwd_f32(const float* V, const float* T, const 
                                           const float* g_side, const float* g_out, int64_t n, int32_t d, float* dV, float* dT,
                                           float* dC, float* dWq, float* dbq, float* dq, float* dWv, float* dbv, float* dWt,
                                           float* dbt, void* workspace, mmrec_stream_t stream) {
-    if (d != MF_D || n > MF_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
+    if (d != MF_D || n > T64_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     const bool want_w = dWq || dbq || dq || dWv || dbv || dWt || dbt;
     if (!V || !T || !C || !Wq || !bq || !q || !Wv || !bv || !Wt || !bt || (want_w && !workspace)) return MMREC_ERR_BAD_ARG;
     if (!want_w && !dV && !dT && !dC) return 0;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(modal_fusion_bwd_kernel), mf_lds_bytes(MF_BWD_TILES), lds_ok);
-    if (rc) return rc;
     hipStream_t s = mmrec_stream(stream);
     float* part = want_w ? static_cast<float*>(workspace) : nullptr;
-    const int nb = mf_blocks(n);
-    hipLaunchKernelGGL(modal_fusion_bwd_kernel, dim3(nb), dim3(T64_BLOCK), mf_lds_bytes(MF_BWD_TILES), s, V, T, C, Wq, bq, q, Wv,
-                       bv, Wt, bt, g_side, g_out, (long)n, mf_rows_per_block(n) / T64, dV, dT, dC, part);
+    const int nb = t64_fuser_blocks(n);
+    const int rc = t64_launch<modal_fusion_bwd_kernel>(nb, mf_lds_bytes(MF_BWD_TILES), s, V, T, C, Wq, bq, q, Wv, bv, Wt, bt, g_side,
+                                                       g_out, (long)n, t64_fuser_rows(n) / T64, dV, dT, dC, part);
+    if (rc) return rc;
     if (want_w)
         hipLaunchKernelGGL(modal_fusion_finish_kernel, dim3(MF_PART / MF_D), dim3(T64_BLOCK), 0, s, part, nb, dWq, dbq, dq, dWv,
                            dbv, dWt, dbt);

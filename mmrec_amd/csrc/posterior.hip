@@ -68,10 +68,6 @@ __device__ __forceinline__ PfPoE pf_poe(float mu_a, PfExpert a, float mu_b, PfEx
     r.l = logf(r.var);
     return r;
 }
-__device__ __forceinline__ float pf_sigmoid(float z) {
-    const float q = expf(-fabsf(z));
-    return (z >= 0.f ? 1.f : q) / (1.f + q);
-}
 __device__ __forceinline__ float pf_get(const float4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 __device__ __forceinline__ void pf_set(float4& v, int j, float x) {
     if (j == 0) v.x = x;
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(PF_BLOCK) void posterior_fwd_kernel(
             pf_set(zt, j, z);
             const float tc = pf_tail(muc, lvc, noisy, pf_get(ec, j), z);
             pf_set(zc, j, z);
-            pf_set(sc, j, pf_sigmoid(s2.m));
+            pf_set(sc, j, stable_sigmoid(s2.m));
             row[0] = j ? row[0] + tp : tp;
             row[1] = j ? row[1] + tv : tv;
             row[2] = j ? row[2] + tt : tt;

@@ -47,7 +47,6 @@ constexpr int SPC_MAX_BLOCKS = 1024;             // more rows than 65,536: more 
 constexpr int SPC_W_LDS = 208;                   // the weights in LDS, padded to a float4 multiple
 constexpr int SPC_FWD_TILES = 4, SPC_BWD_TILES = 6;
 constexpr int SPC_BINS_PER_WAVE = 9;             // wave w of four takes the bins w, w + 4, ...: nine at most
-constexpr int64_t SPC_MAX_ROWS = (int64_t)1 << 30;
 
 // F, F^T and the tiles, all at the T64_LD pitch, and the weights
 constexpr size_t spc_lds_bytes(int tiles) { return sizeof(float) * ((size_t)(2 + tiles) * T64_FLOATS + SPC_W_LDS); }
@@ -269,26 +268,23 @@ __global__ __launch_bounds__(T64_BLOCK) void spectrum_finish_kernel(const float*
 
 }  // namespace
 
-extern "C" int32_t mmrec_spectrum_rows_per_block(int64_t n) { return n < 0 || n > SPC_MAX_ROWS ? 0 : spc_rows_per_block(n); }
+extern "C" int32_t mmrec_spectrum_rows_per_block(int64_t n) { return n < 0 || n > T64_MAX_ROWS ? 0 : spc_rows_per_block(n); }
 
 extern "C" size_t mmrec_spectrum_workspace_bytes(int64_t n) {
-    if (n < 0 || n > SPC_MAX_ROWS) return 0;
+    if (n < 0 || n > T64_MAX_ROWS) return 0;
     return sizeof(float) * (size_t)spc_blocks(n) * SPC_NW;
 }
 
 extern "C" int mmrec_spectrum_fwd_f32(const float* x, const float* y, const float* w_img, const float* w_txt,
                                       const float* w_fus, int64_t n, int32_t d, float* out_img, float* out_txt, float* out_fus,
                                       mmrec_stream_t stream) {
-    if (d != SPC_D || n > SPC_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
+    if (d != SPC_D || n > T64_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     if (!x || !y || !w_img || !w_txt || !w_fus || !out_img || !out_txt || !out_fus) return MMREC_ERR_BAD_ARG;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(spectrum_fwd_kernel), spc_lds_bytes(SPC_FWD_TILES), lds_ok);
+    const int rc = t64_launch<spectrum_fwd_kernel>(spc_blocks(n), spc_lds_bytes(SPC_FWD_TILES), mmrec_stream(stream), x, y, w_img,
+                                                   w_txt, w_fus, (long)n, spc_rows_per_block(n) / T64, out_img, out_txt, out_fus);
     if (rc) return rc;
-    hipLaunchKernelGGL(spectrum_fwd_kernel, dim3(spc_blocks(n)), dim3(T64_BLOCK), spc_lds_bytes(SPC_FWD_TILES),
-                       mmrec_stream(stream), x, y, w_img, w_txt, w_fus, (long)n, spc_rows_per_block(n) / T64, out_img, out_txt,
-                       out_fus);
     MMREC_RETURN_LAUNCH_STATUS();
 }
 
@@ -296,20 +292,18 @@ extern "C" int mmrec_spectrum_bwd_f32(const float* x, const float* y, const floa
                                       const float* w_fus, const float* g_img, const float* g_txt, const float* g_fus, int64_t n,
                                       int32_t d, float* dx, float* dy, float* dw_img, float* dw_txt, float* dw_fus,
                                       void* workspace, mmrec_stream_t stream) {
-    if (d != SPC_D || n > SPC_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
+    if (d != SPC_D || n > T64_MAX_ROWS) return MMREC_ERR_UNSUPPORTED;
     if (n < 0) return MMREC_ERR_BAD_ARG;
     if (n == 0) return 0;
     const bool want_w = dw_img || dw_txt || dw_fus;
     if (!x || !y || !w_img || !w_txt || !w_fus || (want_w && !workspace)) return MMREC_ERR_BAD_ARG;
     if (!want_w && !dx && !dy) return 0;
-    static bool lds_ok[64];
-    const int rc = t64_allow_lds(reinterpret_cast<const void*>(spectrum_bwd_kernel), spc_lds_bytes(SPC_BWD_TILES), lds_ok);
-    if (rc) return rc;
     hipStream_t s = mmrec_stream(stream);
     float* part = want_w ? static_cast<float*>(workspace) : nullptr;
     const int nb = spc_blocks(n);
-    hipLaunchKernelGGL(spectrum_bwd_kernel, dim3(nb), dim3(T64_BLOCK), spc_lds_bytes(SPC_BWD_TILES), s, x, y, w_img, w_txt, w_fus,
-                       g_img, g_txt, g_fus, (long)n, spc_rows_per_block(n) / T64, dx, dy, part);
+    const int rc = t64_launch<spectrum_bwd_kernel>(nb, spc_lds_bytes(SPC_BWD_TILES), s, x, y, w_img, w_txt, w_fus, g_img, g_txt,
+                                                   g_fus, (long)n, spc_rows_per_block(n) / T64, dx, dy, part);
+    if (rc) return rc;
     if (want_w)
         hipLaunchKernelGGL(spectrum_finish_kernel, dim3((SPC_NW + T64_BLOCK / MMREC_WAVE - 1) / (T64_BLOCK / MMREC_WAVE)),
                            dim3(T64_BLOCK), 0, s, part, nb, dw_img, dw_txt, dw_fus);

@@ -119,6 +119,17 @@ def _dev_table(t, width=None, max_rows=None):
                 and (width is None or t.shape[1] == width) and (max_rows is None or t.shape[0] <= max_rows))
 
 
+def _fuser_table(t):
+    """a whole-table fuser's operand (csrc/tile64.h): a device fp32 contiguous [n, 64] table, 1 <= n <= 2^30"""
+    return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
+
+
+def _dev_tensor(t, shape):
+    """a device fp32 contiguous tensor of this shape"""
+    return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                tuple(t.shape) == shape)
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
@@ -2951,14 +2962,9 @@ def spectrum_fusion_torch(image, text, w_img, w_txt, w_fus):
 def spectrum_fusion_served(image, text, w_img, w_txt, w_fus):
     """True where `spectrum_fusion` runs the kernels: device fp32 contiguous [I, 64] tables of one shape, 1 <= I <= 2^30,
     device fp32 contiguous [1, 33, 2] weights, the `SPECTRUM` switch on."""
-    def table(t):
-        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
-
-    def weight(t):
-        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                    tuple(t.shape) == (1, SPECTRUM_BINS, 2))
-    return bool(SPECTRUM and table(image) and table(text) and image.shape == text.shape and image.device == text.device
-                and all(weight(w) and w.device == image.device for w in (w_img, w_txt, w_fus)))
+    return bool(SPECTRUM and _fuser_table(image) and _fuser_table(text) and image.shape == text.shape
+                and image.device == text.device
+                and all(_dev_tensor(w, (1, SPECTRUM_BINS, 2)) and w.device == image.device for w in (w_img, w_txt, w_fus)))
 
 
 class _SpectrumFusion(torch.autograd.Function):
@@ -3037,12 +3043,7 @@ def modal_fusion_torch(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
 def modal_fusion_served(V, T, C, Wq, bq, q, Wv, bv, Wt, bt):
     """True where `modal_fusion` runs the kernels: device fp32 contiguous [n, 64] tables of one shape, 1 <= n <= 2^30, device
     fp32 contiguous [64, 64] matrices, [64] biases and a [1, 64] q, the `MODAL_FUSION` switch on."""
-    def ok(t, shape=None):
-        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                    (shape is None or tuple(t.shape) == shape))
-
-    def table(t):
-        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
+    ok, table = _dev_tensor, _fuser_table
     if not (MODAL_FUSION and table(V) and table(T) and table(C) and V.shape == T.shape == C.shape):
         return False
     return bool(all(ok(w, (EMB_DIM, EMB_DIM)) for w in (Wq, Wv, Wt)) and all(ok(b, (EMB_DIM,)) for b in (bq, bv, bt)) and
@@ -3131,14 +3132,12 @@ def posterior_fusion_torch(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise=None):
 def posterior_fusion_served(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise=None):
     """True where `posterior_fusion` runs the kernels: six device fp32 contiguous [n, 64] tables of one shape on one device,
     1 <= n <= 2^30, the noise None or four more such tables, the `POSTERIOR_FUSION` switch on."""
-    def table(t):
-        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
     tabs = (mu_v, lv_v, mu_t, lv_t, mu_c, lv_c)
     if noise is not None:
         if not isinstance(noise, (tuple, list)) or len(noise) != 4:
             return False
         tabs = tabs + tuple(noise)
-    if not (POSTERIOR_FUSION and all(table(t) for t in tabs)):
+    if not (POSTERIOR_FUSION and all(_fuser_table(t) for t in tabs)):
         return False
     return bool(all(t.shape == mu_v.shape and t.device == mu_v.device for t in tabs))
 
@@ -3222,12 +3221,7 @@ def encoder_heads_served(AX, X, W, b, G, bg, L, bl, scale=None, slope=0.01):
     """True where `encoder_heads` runs the kernels: device fp32 contiguous [n, 64] tables AX and X of one shape, 1 <= n <= 2^30,
     device fp32 contiguous [H, 64, 64] matrices and [H, 64] biases with H in 1 .. 4, `scale` None or such a [H, n, 64] tensor,
     all on one device, the `ENCODER_HEADS` switch on."""
-    def ok(t, shape):
-        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                    tuple(t.shape) == shape)
-
-    def table(t):
-        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
+    ok, table = _dev_tensor, _fuser_table
     if not (ENCODER_HEADS and table(AX) and table(X) and AX.shape == X.shape and isinstance(W, torch.Tensor) and W.dim() == 3):
         return False
     H, n = W.shape[0], AX.shape[0]
@@ -3314,11 +3308,8 @@ def gcn_layer_served(AX, X, R, Wc, Wl, bl, Wg, bg, slope=0.01):
     1 <= n <= 2^30, device fp32 contiguous Wc, Wl [64, 64], Wg [64, 128] and bl, bg [64], all on one device, slope > 0, the
     `GCN_LAYER` switch on."""
     def ok(t, shape):
-        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                    tuple(t.shape) == shape and t.device == AX.device)
-
-    def table(t):
-        return _dev_table(t, EMB_DIM, 1 << 30) and t.shape[0] >= 1
+        return _dev_tensor(t, shape) and t.device == AX.device
+    table = _fuser_table
     if not (GCN_LAYER and table(AX) and table(X) and AX.shape == X.shape and float(slope) > 0.0):
         return False
     if X.device != AX.device or (R is not None and not ok(R, tuple(AX.shape))):

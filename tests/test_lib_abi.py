@@ -156,6 +156,18 @@ def test_tile_and_sweep_plans(lib):
     assert lib.mmrec_tri_topk_split_cols(2048, 7050) == 256
 
 
+def test_row_fusers_share_one_plan(lib):
+    """The three whole-table fusers on tile64.h (modal fusion, encoder heads, GCN layer) have ONE plan, 256 workgroups of 64 rows
+    and then more tiles each, and differ in the floats of a block's partial only.  16,385 rows: 129 blocks of 128 rows, of 12,544
+    floats (3 (64 64 + 64) + 64), of 2 heads x 12,480 (3 (64 64 + 64)) and of 16,512 (4 (64 64) + 2 (64)).  Nothing is launched."""
+    plans = (lib.mmrec_modal_fusion_rows_per_block, lib.mmrec_encoder_heads_rows_per_block, lib.mmrec_gcn_layer_rows_per_block)
+    for n in (0, 1, 64, 65, 16384, 16385, 20011, 2 ** 30, 2 ** 30 + 1, -1):
+        assert len({rows(n) for rows in plans}) == 1, n
+    assert lib.mmrec_modal_fusion_workspace_bytes(16385) == 129 * 12544 * 4 == 6472704
+    assert lib.mmrec_encoder_heads_workspace_bytes(16385, 2) == 129 * 2 * 12480 * 4 == 12879360
+    assert lib.mmrec_gcn_layer_workspace_bytes(16385) == 129 * 16512 * 4 == 8520192
+
+
 def test_projection_workspace_plans(lib):
     """The workspace exports of the modal projection (gemm.hip), which launch nothing: the split plans and the layouts behind them
     pinned to literals.  Notation: blocks = ceil(n / 128) row blocks; the fp32 plan `pick_split` minimises max(ceil(tiles s / 256),

@@ -634,6 +634,50 @@ int mmrec_hyper_layer_bwd_f32(const float* P_i, const float* P_u, const float* X
                               const float* dX, int64_t I, int64_t U, int32_t H, int32_t d, float* dP_i, float* dP_u,
                               float* dX_prev, void* workspace, mmrec_stream_t stream);
 
+/* The same at 64 hyperedges (Clothing's hyper_num; csrc/hypergraph64.hip).  ADDITIVE to ABI 16: six new symbols, nothing existing
+ * changes (mmrec_hyper_* still answer MMREC_ERR_UNSUPPORTED above 8), MMREC_ABI_VERSION stays 16.
+ * H = 64 and d = 64 are fixed: every operand is [n, 64] fp32 row-major, lat is [64, 64].  The formulas, the state kept between
+ * the assignment's two calls (p), the NULL conventions and the order of the argument checks are those of the family above.
+ *
+ * mmrec_hyper64_assign_fwd_f32 / _bwd_f32: 16 lanes per row, lane t holding the entries 4 t .. 4 t + 3.  The maximum and the sum
+ *   ((e0 + e1) + e2) + e3 of a lane's four, then a butterfly over the 16 lanes at the distances 8, 4, 2, 1; exp is expf, the
+ *   quotients are fp32 divisions; the backward's dot product is an fma chain over the lane's four from 0, then the butterfly.
+ *   n < 0: MMREC_ERR_BAD_ARG; n > 2^30: MMREC_ERR_UNSUPPORTED; n == 0: 0, no launch; a NULL logits / noise / P, P == p_soft
+ *   (p_soft / dP / dlogits): MMREC_ERR_BAD_ARG -- in this order, before any launch.
+ * mmrec_hyper64_layer_fwd_f32 / _bwd_f32: three launches each.
+ *   reduce    one workgroup per block of R = mmrec_hyper64_rows_per_block(n) consecutive rows of a side, walked as 64-row tiles;
+ *             part[block][h][c] = ONE chain acc = fma(P[r][h], V[r][c], acc) from 0 over the block's rows in order (R fmas; rows
+ *             past n are zeros).  The backward's dlat = P_i^T dX + P_u^T dU runs the item blocks, then the user blocks, in one
+ *             launch; a NULL gradient adds no blocks.
+ *   finish    per output float, thread `quarter` of four adds the blocks quarter, quarter + 4, ... in order from 0, then the
+ *             four sums are added in order: ceil(blocks / 4) + 3 additions.  A term of lat (dlat) meets at most
+ *             R + ceil(blocks / 4) + 3 roundings (dlat: the larger R, both sides' blocks).
+ *   row pass  X_out[r][c] (U_out, dX_prev) = one chain of 64 fmas from 0 over h ascending of P[r][h] lat[h][c] (dlat).
+ *             dP_i[r][h] = ONE chain of 128 fmas from 0: dX[r][c] lat[h][c] for c ascending, then X_prev[r][c] dlat[h][c] for c
+ *             ascending (a NULL dX: the second 64 alone).  dP_u[r][h] = 64 fmas over dU[r][c] lat[h][c] (a NULL dU: zeros).
+ *             Items and users in one launch, lat (and dlat) in LDS.
+ *   U_out NULL: the user rows are neither computed nor written and P_u is not read.  Any of dP_i / dP_u / dX_prev may be NULL
+ *   (not computed).  I == 0: lat = 0 and U_out = 0; a side of no rows launches nothing.  NO ATOMICS, every order a function of
+ *   I and U alone: two calls on the same inputs give the same bits.  Outputs must not alias inputs.
+ *   I < 0 or U < 0: MMREC_ERR_BAD_ARG; I or U > 2^30: MMREC_ERR_UNSUPPORTED; a NULL lat / workspace, I > 0 with a NULL P_i /
+ *   X_prev / X_out (backward: P_i, and X_prev where dP_i is wanted), U > 0 with a NULL P_u where U_out (dU) is given:
+ *   MMREC_ERR_BAD_ARG -- in this order, before any launch.
+ * mmrec_hyper64_rows_per_block(n): R for a side of n rows: 64 while 256 blocks cover it (n <= 16,384), then
+ *   64 ceil(n / 16,384); 0 for n < 0 or n > 2^30.  mmrec_hyper64_workspace_bytes(I, U) = 4 * 4096 * (1 + blocks(I) + blocks(U)) with
+ *   blocks(n) = ceil(n / R(n)): dlat and one [64][64] partial per block; serves either layer call, 16-byte aligned; 0 for a
+ *   negative count or one above 2^30.  No synchronisation, no allocation, no data-dependent launch shape, capture-safe. */
+int32_t mmrec_hyper64_rows_per_block(int64_t n);
+size_t mmrec_hyper64_workspace_bytes(int64_t I, int64_t U);
+int mmrec_hyper64_assign_fwd_f32(const float* logits, const float* noise, const float* keep, int64_t n, float tau,
+                                 float keep_rate, float* P, float* p_soft, mmrec_stream_t stream);
+int mmrec_hyper64_assign_bwd_f32(const float* p_soft, const float* keep, const float* dP, int64_t n, float tau, float keep_rate,
+                                 float* dlogits, mmrec_stream_t stream);
+int mmrec_hyper64_layer_fwd_f32(const float* P_i, const float* P_u, const float* X_prev, int64_t I, int64_t U, float* U_out,
+                                float* X_out, float* lat, void* workspace, mmrec_stream_t stream);
+int mmrec_hyper64_layer_bwd_f32(const float* P_i, const float* P_u, const float* X_prev, const float* lat, const float* dU,
+                                const float* dX, int64_t I, int64_t U, float* dP_i, float* dP_u, float* dX_prev,
+                                void* workspace, mmrec_stream_t stream);
+
 /* SMORE's spectrum step: rfft of two [n, 64] tables, three complex filters, three irfft, with its backward.
  * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
  * replaces: torch.fft.rfft(dim=1, norm='ortho') of the image and text tables, the element-wise products with

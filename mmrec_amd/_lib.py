@@ -89,6 +89,12 @@ SIGNATURES = {
     "mmrec_hyper_assign_bwd_f32": (c_int32, [_P, _P, _P, c_int64, c_int32, c_float, c_float, _P, _P]),
     "mmrec_hyper_layer_fwd_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "mmrec_hyper_layer_bwd_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "mmrec_hyper64_rows_per_block": (c_int32, [c_int64]),
+    "mmrec_hyper64_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "mmrec_hyper64_assign_fwd_f32": (c_int32, [_P, _P, _P, c_int64, c_float, c_float, _P, _P, _P]),
+    "mmrec_hyper64_assign_bwd_f32": (c_int32, [_P, _P, _P, c_int64, c_float, c_float, _P, _P]),
+    "mmrec_hyper64_layer_fwd_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
+    "mmrec_hyper64_layer_bwd_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "mmrec_spectrum_rows_per_block": (c_int32, [c_int64]),
     "mmrec_spectrum_workspace_bytes": (c_size_t, [c_int64]),
     "mmrec_spectrum_fwd_f32": (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P]),

@@ -2767,7 +2767,7 @@ def pseudo_labels(tables, ids, k=10):
 # Hypergraph message passing of LGMRec (csrc/hypergraph.hip): the Gumbel-softmax assignment with its dropout, the HGNN layer
 # ------------------------------------------------------------------------------------------------
 HYPER = True          # False: every hyper_* call is its `*_torch` composition (A/B runs)
-HYPER_H_MAX = 8       # hyperedges the kernels serve (Clothing's hyper_num = 64 takes the torch path)
+HYPER_H_MAX = 8       # hyperedges the narrow kernels serve; exactly 64 (Clothing's hyper_num) is the hyper64_* family below
 
 
 def hyper_rows_per_block(n):
@@ -2824,8 +2824,8 @@ def hyper_assign(logits, noise, keep_mask=None, tau=1.0, keep_rate=1.0):
     Served by the kernels (`hyper_assign_served`): one launch forward, one backward, the row maximum subtracted as torch does.
     The state kept for the backward is p: without a mask that is the result itself; with a mask a second [n, H] tensor, because
     the dropped entries of P are zero while their logits still get a gradient.
-    EVERY OTHER CASE (CPU tensors, H above 8 -- Clothing's 64 --, other dtypes, non-contiguous operands, the switch off) is
-    `hyper_assign_torch` with stock autograd."""
+    EVERY OTHER CASE (CPU tensors, H above 8, other dtypes, non-contiguous operands, the switch off) is `hyper_assign_torch`
+    with stock autograd.  H = 64 (Clothing) has kernels of its own under `hyper64_assign`; 9 ... 63 have none."""
     if hyper_assign_served(logits, noise, keep_mask):
         return _HyperAssign.apply(logits, noise, keep_mask, float(tau), float(keep_rate))
     return hyper_assign_torch(logits, noise, keep_mask, tau, keep_rate)
@@ -2891,7 +2891,7 @@ def hyper_layer(P_i, P_u, X):
     a finish that adds the blocks' partials in a fixed order, one row pass), X read once and each output written once, lat
     [H, 64] the only state besides the operands.  No atomics: the same bits every call, so `DETERMINISTIC` changes nothing.
     EVERY OTHER CASE (CPU tensors, H above 8, a width other than 64, other dtypes, non-contiguous operands, the switch off) is
-    `hyper_layer_torch` with stock autograd."""
+    `hyper_layer_torch` with stock autograd.  H = 64 (Clothing) has kernels of its own under `hyper64_layer`; 9 ... 63 have none."""
     if hyper_layer_served(P_i, P_u, X):
         return _HyperLayer.apply(P_i, P_u, X)
     return hyper_layer_torch(P_i, P_u, X)
@@ -2911,6 +2911,137 @@ def hyper_propagate(P_i, P_u, E, n_layers):
     for _ in range(n_layers - 1):
         _, X = _HyperLayer.apply(P_i, None, X)
     return _HyperLayer.apply(P_i, P_u, X)
+
+
+# ------------------------------------------------------------------------------------------------
+# ... at 64 hyperedges (csrc/hypergraph64.hip): Clothing's hyper_num, every product a [64 rows] x [64, 64] stage of csrc/tile64.h
+# ------------------------------------------------------------------------------------------------
+HYPER64_H = 64        # the one width this family serves; 9 ... 63 stay on the torch compositions (no shipped setting uses them)
+
+
+def hyper64_rows_per_block(n):
+    """rows of a side of n rows that one workgroup of the 64-hyperedge layer's reduction walks (the library's plan)"""
+    return int(_lib.load().mmrec_hyper64_rows_per_block(int(n)))
+
+
+def _hyper64_table(t):
+    return _dev_table(t, HYPER64_H, 1 << 30)
+
+
+def hyper64_assign_served(logits, noise, keep_mask=None):
+    """True where `hyper64_assign` runs the kernels: device fp32 contiguous [n, 64] operands of one shape, the `HYPER` switch on"""
+    return bool(HYPER and _hyper64_table(logits) and _hyper64_table(noise) and noise.shape == logits.shape and
+                (keep_mask is None or (_hyper64_table(keep_mask) and keep_mask.shape == logits.shape)))
+
+
+class _Hyper64Assign(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, noise, keep, tau, keep_rate):
+        n = logits.shape[0]
+        P = torch.empty_like(logits)
+        p = None if keep is None else torch.empty_like(logits)       # with a mask P has lost p at the dropped entries
+        _lib.check(_lib.load().mmrec_hyper64_assign_fwd_f32(_p(logits), _p(noise), _p(keep), n, tau, keep_rate, _p(P), _p(p),
+                                                            _stream()), "hyper64_assign_fwd")
+        ctx.tau, ctx.keep_rate, ctx.masked = tau, keep_rate, keep is not None
+        ctx.save_for_backward(*((p, keep) if ctx.masked else (P,)))
+        return P
+
+    @staticmethod
+    def backward(ctx, dP):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        p, keep = ctx.saved_tensors if ctx.masked else (ctx.saved_tensors[0], None)
+        da = torch.empty_like(p)
+        _lib.check(_lib.load().mmrec_hyper64_assign_bwd_f32(_p(p), _p(keep), _p(dP.contiguous()), p.shape[0], ctx.tau,
+                                                            ctx.keep_rate, _p(da), _stream()), "hyper64_assign_bwd")
+        return da, None, None, None, None
+
+
+def hyper64_assign(logits, noise, keep_mask=None, tau=1.0, keep_rate=1.0):
+    """`hyper_assign` at 64 hyperedges -> P [n, 64]: p = softmax((logits + noise) / tau) over a row, P = p * keep_mask /
+    keep_rate (no mask: P = p); nothing is drawn here; differentiable in `logits` only.
+    Served by the kernels (`hyper64_assign_served`): one launch each way, 16 lanes per row, the row maximum subtracted.  The state
+    kept for the backward is what `hyper_assign` keeps: P alone without a mask, p and the mask with one.
+    EVERY OTHER CASE (CPU tensors, any other width, other dtypes, non-contiguous operands, the switch off) is
+    `hyper_assign_torch` with stock autograd."""
+    if hyper64_assign_served(logits, noise, keep_mask):
+        return _Hyper64Assign.apply(logits, noise, keep_mask, float(tau), float(keep_rate))
+    return hyper_assign_torch(logits, noise, keep_mask, tau, keep_rate)
+
+
+def hyper64_layer_served(P_i, P_u, X):
+    """True where `hyper64_layer` runs the kernels: device fp32 contiguous P_i [I, 64], P_u [U, 64], X [I, 64], the `HYPER`
+    switch on"""
+    return bool(HYPER and _hyper64_table(P_i) and _hyper64_table(P_u) and _dev_table(X, EMB_DIM, 1 << 30)
+                and P_i.shape[0] == X.shape[0])
+
+
+class _Hyper64Layer(torch.autograd.Function):
+    """forward(P_i, P_u or None where U_out is not wanted, X) -> (U_out or None, X_out)"""
+
+    @staticmethod
+    def forward(ctx, P_i, P_u, X):
+        lib = _lib.load()
+        I, U = P_i.shape[0], 0 if P_u is None else P_u.shape[0]
+        lat = torch.empty(HYPER64_H, EMB_DIM, dtype=torch.float32, device=X.device)
+        X_out = torch.empty_like(X)
+        U_out = None if P_u is None else torch.empty(U, EMB_DIM, dtype=torch.float32, device=X.device)
+        ws = _ws(lib.mmrec_hyper64_workspace_bytes(I, U), X.device)
+        _lib.check(lib.mmrec_hyper64_layer_fwd_f32(_p(P_i), _p(P_u), _p(X), I, U, _p(U_out), _p(X_out), _p(lat), _p(ws), _stream()),
+                   "hyper64_layer_fwd")
+        ctx.has_u = P_u is not None
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*((P_i, X, lat, P_u) if ctx.has_u else (P_i, X, lat)))
+        return U_out, X_out
+
+    @staticmethod
+    def backward(ctx, dU, dX):
+        P_i, X, lat = ctx.saved_tensors[:3]
+        P_u = ctx.saved_tensors[3] if ctx.has_u else None
+        want_pi, want_pu, want_x = ctx.needs_input_grad[0], ctx.has_u and ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want_pi or want_pu or want_x):
+            return None, None, None
+        lib = _lib.load()
+        I, U = P_i.shape[0], 0 if P_u is None else P_u.shape[0]
+        dU = None if (dU is None or P_u is None) else dU.contiguous()
+        dX = None if dX is None else dX.contiguous()
+        dP_i = torch.empty_like(P_i) if want_pi else None
+        dP_u = torch.empty_like(P_u) if want_pu else None
+        dX_prev = torch.empty_like(X) if want_x else None
+        ws = _ws(lib.mmrec_hyper64_workspace_bytes(I, U), X.device)
+        _lib.check(lib.mmrec_hyper64_layer_bwd_f32(_p(P_i), _p(P_u), _p(X), _p(lat), _p(dU), _p(dX), I, U, _p(dP_i), _p(dP_u),
+                                                   _p(dX_prev), _p(ws), _stream()), "hyper64_layer_bwd")
+        return dP_i, dP_u, dX_prev
+
+
+def hyper64_layer(P_i, P_u, X):
+    """`hyper_layer` at 64 hyperedges -> (U_out [U, 64], X_out [I, 64]): lat = P_i^T X [64, 64];  X_out = P_i lat;  U_out = P_u lat,
+    differentiable in all three operands.
+    Served by the kernels (`hyper64_layer_served`): three launches each way -- a reduce over blocks of `hyper64_rows_per_block`
+    rows (one fma chain per block, in row order), a finish that adds the blocks' partials in a fixed order, one row pass over
+    items and users with lat in LDS.  The state is what `hyper_layer` keeps: P_i, X, lat [64, 64] and P_u where it was given.  No
+    atomics: the same bits every call.
+    EVERY OTHER CASE (CPU tensors, any other width, other dtypes, non-contiguous operands, the switch off) is `hyper_layer_torch`
+    with stock autograd."""
+    if hyper64_layer_served(P_i, P_u, X):
+        return _Hyper64Layer.apply(P_i, P_u, X)
+    return hyper_layer_torch(P_i, P_u, X)
+
+
+def hyper64_propagate(P_i, P_u, E, n_layers):
+    """`hyper_propagate` at 64 hyperedges: `n_layers` HGNN layers from X_0 = E -> (U_L, X_L).  The served path asks the inner
+    layers for X alone (their user rows are neither computed nor written)."""
+    if n_layers < 1:
+        raise _lib.MMRecHipError("hyper64_propagate: n_layers must be at least 1, got %r" % (n_layers,))
+    if not hyper64_layer_served(P_i, P_u, E):
+        X = E
+        for _ in range(n_layers):
+            U_out, X = hyper_layer_torch(P_i, P_u, X)
+        return U_out, X
+    X = E
+    for _ in range(n_layers - 1):
+        _, X = _Hyper64Layer.apply(P_i, None, X)
+    return _Hyper64Layer.apply(P_i, P_u, X)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -11,7 +11,13 @@ forward: CGE = fused LightGCN layer mean; MGE = modal projection X W on the fp32
          `hip_ops.hyper_propagate` (csrc/hypergraph.hip: lat = P_i^T X reduced over row blocks in a fixed order, both outputs
          expanded in one pass; no atomics).  The kernels draw nothing: `_hyper_noise` and `_hyper_keep` draw what
          F.gumbel_softmax and F.dropout draw -- the same distributions, NOT the same generator stream, so a seeded run with
-         the key on is not step-identical to one with it off.  hyper_num above 8 (Clothing: 64) takes the torch composition
+         the key on is not step-identical to one with it off.  hyper_num = 64 (Clothing) takes the 64-hyperedge family
+         `hip_ops.hyper64_assign` / `hyper64_propagate` (csrc/hypergraph64.hip: every product a [64 rows] x [64, 64] stage), and
+         there the logits X V are the projection kernel's shape (`hip_ops.linear`, as `mge` computes X W) and R (X V) a plain
+         64-wide SpMM.  At wide features (F >= 1024: the 4096-wide image table) that projection is `hip_ops.linear`'s
+         split-operand form, as `mge`'s X W already is: its accuracy against an fp32 product rests on the projection's own
+         tests (the tiny golden dataset's widths, which the key-on / key-off parity test runs, stay below that threshold).
+         hyper_num 9 ... 63 has no kernels (no shipped setting uses it): the torch composition
 loss   : fused BPR + EmbLoss on the batch rows; the hypergraph contrastive term scores the batch against EVERY
          user / item (B x N logits, lgmrec.py:157-164), not in-batch: torch matmul.  With the config key `fused_ssl: True`
          (absent / False: that path, untouched) the term is `hip_ops.score_lse` -- the row-wise log-sum-exp on the fp32 MFMA
@@ -119,21 +125,26 @@ class LGMRec(FusedEvalMixin, GeneralRecommender):
         return torch.bernoulli(torch.full_like(x, self.keep_rate))
 
     def _forward_fused_hyper(self):
-        """`forward` with `fused_hyper: True`: the same mathematics through hip_ops.hyper_assign / hyper_propagate.  The noise
+        """`forward` with `fused_hyper: True`: the same mathematics through hip_ops.hyper_assign / hyper_propagate (hyper_num = 64:
+        hyper64_assign / hyper64_propagate; 9 ... 63: those wrappers' torch fallback).  The noise
         is drawn in the reference's order (iv, uv, it, ut), then the masks in the same order; the draws follow F.gumbel_softmax's
         and F.dropout's distributions but not their generator stream, so a seeded run is not step-identical to the key-off path."""
+        wide = self.hyper_num == hip_ops.HYPER64_H                      # Clothing's 64 hyperedges: the family of csrc/hypergraph64.hip
+        assign, propagate = ((hip_ops.hyper64_assign, hip_ops.hyper64_propagate) if wide
+                             else (hip_ops.hyper_assign, hip_ops.hyper_propagate))
         logits = []
         for feat, w in ((self.image_embedding.weight, self.v_hyper), (self.text_embedding.weight, self.t_hyper)):
-            i_h = torch.mm(feat, w)
+            # [n, F] x [F, 64] is the projection kernel's shape (as `mge`: W is stored [F, 64], transposed per step)
+            i_h = hip_ops.linear(feat, w.t().contiguous(), None) if (wide and feat.shape[1] % 4 == 0) else torch.mm(feat, w)
             logits += [i_h, hip_ops.spmm(self.adj, i_h).contiguous()]    # (the SpMM's result is a view of its 64-float rows)
         noise = [self._hyper_noise(a) for a in logits]
         cge_embs = self.cge()
         lge_embs = cge_embs + F.normalize(self.mge('v')) + F.normalize(self.mge('t'))
         keep = [self._hyper_keep(a) for a in logits]
-        iv_p, uv_p, it_p, ut_p = (hip_ops.hyper_assign(a, g, m, self.tau, self.keep_rate) for a, g, m in zip(logits, noise, keep))
+        iv_p, uv_p, it_p, ut_p = (assign(a, g, m, self.tau, self.keep_rate) for a, g, m in zip(logits, noise, keep))
         items = cge_embs[self.n_users:]
-        uv, iv = hip_ops.hyper_propagate(iv_p, uv_p, items, self.n_hyper_layer)
-        ut, it = hip_ops.hyper_propagate(it_p, ut_p, items, self.n_hyper_layer)
+        uv, iv = propagate(iv_p, uv_p, items, self.n_hyper_layer)
+        ut, it = propagate(it_p, ut_p, items, self.n_hyper_layer)
         ghe_embs = torch.cat([uv, iv], dim=0) + torch.cat([ut, it], dim=0)
         all_embs = lge_embs + self.alpha * F.normalize(ghe_embs)
         return all_embs[:self.n_users], all_embs[self.n_users:], [uv, iv, ut, it]

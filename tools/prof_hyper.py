@@ -9,13 +9,16 @@ softmax / dropout chain and three torch.mm per layer with stock autograd) in ONE
                       4 B x 64 x (2 I + U) (E read, X' and U' written) + 4 B x H x (I + U) (the assignments)
 
 Sizes (I items, U users), H = 4, tau = 0.2, keep rate 0.5, one layer: Amazon-Baby 7,050 / 19,445, Amazon-Sports 18,357 /
-35,598, and the 500,000 / 1,000,000 table of config 5.  HIP events around windows of replays: median / min / max over five
+35,598, and the 500,000 / 1,000,000 table of config 5.  `--hyper-num 64` takes the 64-hyperedge family (hyper64_assign +
+hyper64_propagate, csrc/hypergraph64.hip) against the same composition; `--layers`, `--keep` and `--sizes` (names of the table
+below, among them Amazon-Clothing's 23,033 / 39,387) set the rest: Clothing's setting is `--hyper-num 64 --layers 2 --keep 0.2`.  HIP events around windows of replays: median / min / max over five
 windows after warm-up, windows of the two paths alternating.  A leg is "slower" when its median exceeds the composition's by more
 than the composition's own min-max spread.  Peak memory: one eager forward + backward above the resident inputs.  Results as JSON
 (default profiles/hyper_ab.json).
 
-    python tools/prof_hyper.py [out.json]
+    python tools/prof_hyper.py [out.json] [--hyper-num H] [--layers L] [--keep Q] [--sizes baby,clothing,...]
 """
+import argparse
 import json
 import os
 import sys
@@ -25,6 +28,7 @@ sys.path.insert(0, ROOT)
 
 WINDOWS = 5
 SIZES = (("baby", 7050, 19445, 200), ("sports", 18357, 35598, 200), ("config5", 500000, 1000000, 20))
+MORE_SIZES = (("clothing", 23033, 39387, 200),)      # by name only (--sizes)
 H, TAU, KEEP, LAYERS, D = 4, 0.2, 0.5, 1, 64
 
 
@@ -68,7 +72,12 @@ def one(name, I, U, replays):
     g_i, g_u = (-torch.empty(n, H, device=dev).exponential_(generator=gen).log() for n in (I, U))
     m_i, m_u = (torch.bernoulli(torch.full((n, H), KEEP, device=dev), generator=gen) for n in (I, U))
     w_u, w_x = r(U, D), r(I, D)
-    assert hip_ops.hyper_assign_served(a_i, g_i, m_i) and hip_ops.hyper_layer_served(a_i.detach(), a_u.detach(), E.detach())
+    wide = H == hip_ops.HYPER64_H
+    assign, propagate, layer, assign_served, layer_served = (
+        (hip_ops.hyper64_assign, hip_ops.hyper64_propagate, hip_ops.hyper64_layer, hip_ops.hyper64_assign_served,
+         hip_ops.hyper64_layer_served) if wide else
+        (hip_ops.hyper_assign, hip_ops.hyper_propagate, hip_ops.hyper_layer, hip_ops.hyper_assign_served, hip_ops.hyper_layer_served))
+    assert assign_served(a_i, g_i, m_i) and layer_served(a_i.detach(), a_u.detach(), E.detach())
 
     def with_switch(on, fn):
         def run():
@@ -80,8 +89,8 @@ def one(name, I, U, replays):
         return run
 
     def forward_value():
-        P_i, P_u = hip_ops.hyper_assign(a_i, g_i, m_i, TAU, KEEP), hip_ops.hyper_assign(a_u, g_u, m_u, TAU, KEEP)
-        return hip_ops.hyper_propagate(P_i, P_u, E, LAYERS)
+        P_i, P_u = assign(a_i, g_i, m_i, TAU, KEEP), assign(a_u, g_u, m_u, TAU, KEEP)
+        return propagate(P_i, P_u, E, LAYERS)
 
     def forward():
         with torch.no_grad():
@@ -96,9 +105,9 @@ def one(name, I, U, replays):
 
     def layer_forward():
         with torch.no_grad():
-            return hip_ops.hyper_layer(P_i0, P_u0, E)
+            return layer(P_i0, P_u0, E)
 
-    result = {"shape": name, "n_items": I, "n_users": U, "hyper_num": H, "layers": LAYERS, "windows": WINDOWS,
+    result = {"shape": name, "n_items": I, "n_users": U, "hyper_num": H, "layers": LAYERS, "keep_rate": KEEP, "windows": WINDOWS,
               "replays_per_window": replays, "legs": {}, "peak_mb_forward_backward": {}, "max_diff": {}}
     got = {}
     for k, on in (("kernel", True), ("composition", False)):
@@ -145,8 +154,16 @@ def one(name, I, U, replays):
 
 
 if __name__ == "__main__":
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "hyper_ab.json")
-    results = [one(*s) for s in SIZES]
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "hyper_ab.json"))
+    ap.add_argument("--hyper-num", type=int, default=H)
+    ap.add_argument("--layers", type=int, default=LAYERS)
+    ap.add_argument("--keep", type=float, default=KEEP)
+    ap.add_argument("--sizes", default=",".join(s[0] for s in SIZES))
+    args = ap.parse_args()
+    path, H, LAYERS, KEEP = args.out, args.hyper_num, args.layers, args.keep
+    table = {s[0]: s for s in SIZES + MORE_SIZES}
+    results = [one(*table[n]) for n in args.sizes.split(",")]
     with open(path, "w") as f:
         json.dump(results, f, indent=1)
     print("wrote", path)

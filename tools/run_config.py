@@ -47,6 +47,9 @@ CONFIGS = {
     "dragon": ("DRAGON", "baby", {"aggr_mode": "add", "reg_weight": 1e-3, "learning_rate": 1e-3}),
     "lgmrec": ("LGMRec", "baby", {"n_ui_layers": 2, "n_mm_layers": 2, "n_hyper_layer": 1, "hyper_num": 4,
                                   "keep_rate": 0.5, "alpha": 0.3, "cl_weight": 1e-4, "reg_weight": 1e-6}),
+    # the reference's Clothing setting of LGMRec: 64 hyperedges, two hypergraph layers (with fused_hyper: csrc/hypergraph64.hip)
+    "lgmrec_clothing": ("LGMRec", "clothing", {"n_ui_layers": 2, "n_mm_layers": 2, "n_hyper_layer": 2, "hyper_num": 64,
+                                               "keep_rate": 0.2, "alpha": 0.3, "cl_weight": 1e-4, "reg_weight": 1e-6}),
 }
 
 
@@ -125,8 +128,8 @@ def main():
                                                                        "hyper_propagate) and RUNS with it off, alternated in this process")
     args = ap.parse_args()
     cd = dict(device_neg_sampling=args.device_neg_sampling)
-    if args.fused_hyper_ab and args.config != "lgmrec":
-        ap.error("fused_hyper is a key of LGMRec: use it with `lgmrec`")
+    if args.fused_hyper_ab and args.config not in ("lgmrec", "lgmrec_clothing"):
+        ap.error("fused_hyper is a key of LGMRec: use it with `lgmrec` or `lgmrec_clothing`")
     if args.fused_ssl or args.fused_ssl_ab:
         if args.config not in ("lgmrec", "pgl", "pgl_cl"):
             ap.error("fused_ssl is a key of LGMRec and PGL: use it with `lgmrec` or `pgl_cl` (`pgl` has the term's weight at 0)")

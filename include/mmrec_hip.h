@@ -997,6 +997,65 @@ int mmrec_tri_topk_f32(const float* T0, const float* T1, const float* T2, int32_
 int mmrec_list_exclude_i32(const int32_t* cand, const int32_t* excl, int32_t R, int32_t kc, int32_t ke, int32_t k, int32_t* out,
                            mmrec_stream_t stream);
 
+/* MVGAE's reconstruction term: every batch user against the HARDEST of the batch's negatives, for L latents over the same rows,
+ * never storing the sigmoid of a table, a gathered block or the [B, B] scores; with its backward.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: recon_loss / dot_product_decode_neg -- mvgae.py:73-85,164-170 -- four times a step, and autograd's mirror of it.
+ *
+ * Z [L, N, 64] fp32 row-major, 1 <= L <= 8, 1 <= N <= 2^30; users, pos, neg [B] int64 row ids into every Z[l], 1 <= B <= 65,536.
+ * With S = sigmoid(Z[l]) (squash != 0; the sigmoid of mmrec_posterior_fusion_fwd_f32: q = expf(-|z|), (z >= 0 ? 1 : q) / (1 + q))
+ * or S = Z[l] (squash == 0), u_b = S[users[b]], p_b = S[pos[b]], n_j = S[neg[j]]:
+ *   dp_b = <u_b, p_b>,  a_b = sigmoid(dp_b)
+ *   h_b  = max_j <u_b, n_j> over the CANDIDATES j: the positions j < B with neg[j] in [0, N)
+ *   arg_b = the LOWEST candidate position that attains h_b                                            arg [L, B] int32
+ *   x_b = a_b - sigmoid(h_b),  term_b = softplus(-x_b) / ln 2 = -log2(sigmoid(x_b)),  loss[l] = sum_b term_b         loss [L]
+ *   c1_b = dterm / d dp = -(sg (a (1 - a))),  c2_b = dterm / dh = sg (sh (1 - sh)),  sg = sigmoid(-x_b) / ln 2, sh = sigmoid(h_b)
+ *                                                                                      coef [L, B, 2] = (c1, c2)
+ *   su [L, B, 64] = u_b, the squashed user rows (zeros for a sample that does not contribute), kept for the backward
+ * AN ID OUTSIDE [0, N) IS NEVER AN ADDRESS.  A sample b with users[b] or pos[b] out of range, or without any candidate, does not
+ * contribute: term 0, arg -1, c1 = c2 = 0.  A negative out of range is no candidate for anybody.
+ *
+ * THE PLAN.  mmrec_hardest_neg_fwd_f32 is three launches.
+ *   sweep    grid (ceil(B / 128) own tiles) x (splits of the negatives) x L; a split walks mmrec_hardest_neg_split_cols(B, L)
+ *            negative positions (a multiple of 64, a function of B and L alone: ceil(B / 64) tiles over at most 16 splits, about
+ *            ceil(512 / L) workgroups a latent).  Scores are the fp32 fma chains of the fp32-input MFMA in natural k order,
+ *            score(b, j) = fma(n_j[63], u_b[63], ... fma(n_j[1], u_b[1], n_j[0] u_b[0])) -- the same roundings at every position,
+ *            so equal rows score equal bits.  Selection compares (score, then the lower position) in every lane, between the two
+ *            lanes of a user and between splits: it depends on no accumulator order, tile or split.  A tile row that is no
+ *            candidate is excluded by a mask, never given a score of its own.  One (max, arg) per (split, l, b).
+ *   terms    a thread per (l, b): the splits in order from 0, dp as ONE fma chain from 0 over k = 0 .. 63 of u[k] p[k], then
+ *            (one rounding each, expf / log1pf the library's) a = sigmoid(dp), sh = sigmoid(h), x = a - sh,
+ *            term = (fmaxf(-x, 0) + log1pf(expf(-|x|))) (1 / ln 2), sg = sigmoid(-x) (1 / ln 2), c1 = -(sg (a (1 - a))),
+ *            c2 = sg (sh (1 - sh)); arg, coef and su are written, the term goes to the workspace.
+ *   loss     ONE workgroup of 1,024 threads per latent: thread t adds the terms of the samples t, t + 1024, ... in order from 0
+ *            (ceil(B / 1024) additions), the 64 lanes of a wave by a butterfly (xor 32, 16, 8, 4, 2, 1): 6, the 16 waves in
+ *            order from 0: 16.
+ * mmrec_hardest_neg_bwd_f32: ONE launch, given arg, coef and su of the forward and g [L] ON THE DEVICE (never read by the host),
+ *   writes the SLOT gradients G [L, 3 B, 64], slots in the order users, pos, neg; a 16-lane group per user or pos slot, a WAVE
+ *   per neg slot (the hardest negative of a batch is the same for most of its users: one slot's chain can be B long, and its
+ *   owner reads the kept rows su 16 at a time); w1_b = g[l] c1_b, w2_b = g[l] c2_b:
+ *     user slot b   t = fma(w2_b, n_arg_b, w1_b p_b)
+ *     pos slot b    t = w1_b u_b
+ *     neg slot j    t = the fma chain from 0, over the samples b with arg_b == j in ASCENDING b, of fma(w2_b, u_b, t)
+ *   G = t (s (1 - s)) with s the slot's own squashed row (squash == 0: G = t).  A slot whose sample does not contribute, or whose
+ *   own id is out of range, is zeros.  The caller adds G[l] into dZ[l] at cat(users, pos, neg) with
+ *   mmrec_scatter_add_rows_sorted_f32 (one stable sort for all latents).  G NULL: 0, no launch.
+ * NO FLOAT ATOMICS, every order fixed by (B, L) alone: two calls on the same inputs give the same bits.
+ * workspace: mmrec_hardest_neg_workspace_bytes(B, L) = 4 (2 splits + 1) L B bytes (0 outside the served range), the forward's only.
+ * B == 0 CONTRACT: 0 is returned before any pointer is looked at, nothing is launched and NOTHING IS WRITTEN -- loss keeps the
+ * caller's bytes (a caller that wants the empty sum writes its own zeros).
+ * d != 64, L outside 1 .. 8, B outside 0 .. 65,536, N outside 1 .. 2^30: MMREC_ERR_BAD_ARG; B == 0: 0; a NULL Z / users / pos / neg,
+ * a NULL loss / arg / coef / su / workspace (forward), a NULL arg / coef / su / g with a G (backward): MMREC_ERR_BAD_ARG -- in this order,
+ * before any pointer is followed.  No synchronisation, no allocation, no data-dependent address or launch shape, capture-safe. */
+int32_t mmrec_hardest_neg_split_cols(int32_t B, int32_t L);
+size_t mmrec_hardest_neg_workspace_bytes(int32_t B, int32_t L);
+int mmrec_hardest_neg_fwd_f32(const float* Z, int64_t N, int32_t L, int32_t d, const int64_t* users, const int64_t* pos,
+                              const int64_t* neg, int32_t B, int32_t squash, float* loss, int32_t* arg, float* coef, float* su,
+                              void* workspace, mmrec_stream_t stream);
+int mmrec_hardest_neg_bwd_f32(const float* Z, int64_t N, int32_t L, int32_t d, const int64_t* users, const int64_t* pos,
+                              const int64_t* neg, int32_t B, int32_t squash, const int32_t* arg, const float* coef,
+                              const float* su, const float* g, float* G, mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

@@ -3326,6 +3326,115 @@ def posterior_fusion(mu_v, lv_v, mu_t, lv_t, mu_c, lv_c, noise=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# MVGAE's reconstruction term (csrc/hardest_neg.hip): every batch user against the hardest of the batch's negatives
+# ------------------------------------------------------------------------------------------------
+HARDEST_NEGATIVE = True   # False: every hardest_negative_loss call is `hardest_negative_loss_torch` (A/B runs)
+HARDEST_NEGATIVE_L_MAX = 8
+HARDEST_NEGATIVE_B_MAX = 65536
+
+
+def hardest_negative_split_cols(B, L):
+    """negative positions one workgroup of the sweep walks (the library's plan for the shape; 0 outside the served range)"""
+    return int(_lib.load().mmrec_hardest_neg_split_cols(int(B), int(L)))
+
+
+def hardest_negative_loss_torch(Z, users, pos, neg, squash=True, return_arg=False):
+    """MVGAE.recon_loss (models/mvgae.py) line for line, for each of the L latents of Z [L, N, d] -> loss [L] (and arg [L, B]
+    int32): S = sigmoid(Z[l]) or Z[l]; a = sigmoid(<S[users], S[pos]>); the [B, B] product of the batch's users against the
+    batch's negatives by torch.mm, its row maximum with the argmax RESOLVED TO THE LOWEST POSITION that attains it (torch.max
+    leaves the choice among ties open: the value is the same, the gradient goes to that one negative and the user, the rule
+    the kernels state); -sum log2(sigmoid(a - sigmoid(h))).  Stock autograd.  The composition `hardest_negative_loss` falls
+    back to; its temporaries are the squashed table and [B, B]."""
+    losses, args = [], []
+    for l in range(Z.shape[0]):
+        z = torch.sigmoid(Z[l]) if squash else Z[l]
+        zu = z[users]
+        a = torch.sigmoid((zu * z[pos]).sum(dim=1))
+        scores = torch.mm(zu, z[neg].t())
+        with torch.no_grad():
+            top = scores.max(dim=-1).values
+            where = torch.arange(scores.shape[1], device=scores.device).expand_as(scores)
+            arg = torch.where(scores == top.unsqueeze(1), where, torch.full_like(where, scores.shape[1])).min(dim=1).values
+        hardest = scores.gather(1, arg.unsqueeze(1)).squeeze(1)
+        losses.append(-torch.sum(torch.log2(torch.sigmoid(a - torch.sigmoid(hardest)))))
+        args.append(arg.to(torch.int32))
+    loss = torch.stack(losses)
+    return (loss, torch.stack(args)) if return_arg else loss
+
+
+def hardest_negative_loss_served(Z, users, pos, neg):
+    """True where `hardest_negative_loss` runs the kernels: Z device fp32 contiguous [L, N, 64] with 1 <= L <= 8 and
+    1 <= N <= 2^30, three device int64 contiguous 1-D id tensors of one length 1 <= B <= 65,536, the `HARDEST_NEGATIVE`
+    switch on."""
+    def ids(t):
+        return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous())
+    if not (HARDEST_NEGATIVE and isinstance(Z, torch.Tensor) and Z.is_cuda and Z.dtype == torch.float32 and Z.dim() == 3
+            and Z.is_contiguous() and Z.shape[2] == EMB_DIM and 1 <= Z.shape[0] <= HARDEST_NEGATIVE_L_MAX
+            and 1 <= Z.shape[1] <= 1 << 30):
+        return False
+    return bool(ids(users) and ids(pos) and ids(neg) and users.shape == pos.shape == neg.shape
+                and 1 <= users.shape[0] <= HARDEST_NEGATIVE_B_MAX)
+
+
+class _HardestNegative(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Z, users, pos, neg, squash):
+        lib = _lib.load()
+        L, N, B = Z.shape[0], Z.shape[1], users.shape[0]
+        loss = torch.empty(L, dtype=torch.float32, device=Z.device)
+        arg = torch.empty(L, B, dtype=torch.int32, device=Z.device)
+        coef = torch.empty(L, B, 2, dtype=torch.float32, device=Z.device)
+        su = torch.empty(L, B, EMB_DIM, dtype=torch.float32, device=Z.device)       # the squashed user rows, for the backward
+        ws = _ws(lib.mmrec_hardest_neg_workspace_bytes(B, L), Z.device)
+        _lib.check(lib.mmrec_hardest_neg_fwd_f32(_p(Z), N, L, EMB_DIM, _p(users), _p(pos), _p(neg), B, int(squash), _p(loss),
+                                                 _p(arg), _p(coef), _p(su), _p(ws), _stream()), "hardest_neg_fwd")
+        ctx.squash = int(squash)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(arg)
+        ctx.save_for_backward(Z, users, pos, neg, arg, coef, su)
+        return loss, arg
+
+    @staticmethod
+    def backward(ctx, g, _):
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        lib = _lib.load()
+        Z, users, pos, neg, arg, coef, su = ctx.saved_tensors
+        L, N, B = Z.shape[0], Z.shape[1], users.shape[0]
+        g = g.contiguous()
+        G = torch.empty(L, 3 * B, EMB_DIM, dtype=torch.float32, device=Z.device)
+        _lib.check(lib.mmrec_hardest_neg_bwd_f32(_p(Z), N, L, EMB_DIM, _p(users), _p(pos), _p(neg), B, ctx.squash, _p(arg),
+                                                 _p(coef), _p(su), _p(g), _p(G), _stream()), "hardest_neg_bwd")
+        ids = torch.cat((users, pos, neg))
+        order = torch.sort(ids, stable=True)[1]                        # one sort, shared by the L scatters
+        dZ = torch.zeros_like(Z)
+        for l in range(L):
+            _lib.check(lib.mmrec_scatter_add_rows_sorted_f32(_p(order), _p(ids), _p(G[l]), 3 * B, EMB_DIM, _p(dZ[l]), _stream()),
+                       "scatter_add_rows_sorted")
+        return dZ, None, None, None, None
+
+
+def hardest_negative_loss(Z, users, pos, neg, squash=True, return_arg=False):
+    """MVGAE's reconstruction term (mvgae.py, recon_loss) for L latents over the same rows -> loss [L] (and, with `return_arg`,
+    the detached arg [L, B] int32): with S = sigmoid(Z[l]) (`squash`) or Z[l], u_b = S[users[b]], p_b = S[pos[b]],
+    n_j = S[neg[j]]:  a_b = sigmoid(<u_b, p_b>), h_b = max_j <u_b, n_j> over ALL B negatives of the batch, arg_b the LOWEST
+    position that attains it, loss[l] = -sum_b log2(sigmoid(a_b - sigmoid(h_b))).  The ids are row ids into Z, used as given.
+    Differentiable in Z only; through the maximum the gradient reaches n_arg_b and u_b only.
+    Served by the kernels (`hardest_negative_loss_served`): three launches forward (the fp32-MFMA sweep of 128 users against
+    64-negative tiles, both sides gathered and squashed on the way, a running (score, position) per lane; the terms with the
+    positive dot products and the coefficients; the sum in a fixed tree), one backward that writes the gradients of the 3 B
+    gathered rows, then one stable sort and L calls of the sorted row scatter into a zeroed dZ.  No squashed table, no
+    gathered block, no [B, B] block; no float atomics: the same bits every call, so `DETERMINISTIC` changes nothing;
+    capturable.
+    EVERY OTHER CASE (CPU tensors, a width other than 64, other dtypes, non-contiguous operands, more than 8 latents, more
+    than 65,536 samples, the switch off) is `hardest_negative_loss_torch` with stock autograd: the same rule."""
+    if hardest_negative_loss_served(Z, users, pos, neg):
+        loss, arg = _HardestNegative.apply(Z, users, pos, neg, bool(squash))
+        return (loss, arg) if return_arg else loss
+    return hardest_negative_loss_torch(Z, users, pos, neg, squash, return_arg)
+
+
+# ------------------------------------------------------------------------------------------------
 # MVGAE's encoder heads (csrc/encoder_heads.hip): H normalised convolutions of one aggregated table, output and skip Linears
 # ------------------------------------------------------------------------------------------------
 ENCODER_HEADS = True   # False: every encoder_heads call is `encoder_heads_torch` (A/B runs)

@@ -34,6 +34,12 @@ With the config key `fused_heads: True` (absent / False: the four lines at the e
 spmm(graph, x W) = AX W -- and one `hip_ops.encoder_heads` call (csrc/encoder_heads.hip: one launch forward, two backward) for
 the two normalised convolutions, their dropouts (two masks drawn in the composition's order, mu then logvar), the four
 leaky-ReLUs and the four 64 x 64 Linears.  The trunk convolutions stay as they are: conv_embed_1 is 128 wide.
+
+With the config key `fused_recon: True` (absent / False: `recon_loss` and the batched lines of `_fused_loss`, untouched;
+independent of the other two keys) the reconstruction terms are `hip_ops.hardest_negative_loss` (csrc/hardest_neg.hip: three
+launches forward, one backward and the sorted row scatter): with `fused_posterior` on, ONE call on the stacked z [4, N, 64];
+with it off, four calls on z.unsqueeze(0).  No squashed table, no gathered rows, no [B, B] block; the maximum's gradient goes
+to the LOWEST position that attains it.
 """
 import math
 
@@ -157,6 +163,7 @@ class MVGAE(FusedEvalMixin, GeneralRecommender):
         self.beta = config['beta']
         self.fused_posterior = bool(config['fused_posterior']) if 'fused_posterior' in config else False    # new key, default off
         self.fused_heads = bool(config['fused_heads']) if 'fused_heads' in config else False                # new key, default off
+        self.fused_recon = bool(config['fused_recon']) if 'fused_recon' in config else False                # new key, default off
         num_layer = config['n_layers']
         if self.v_feat is None or self.t_feat is None:
             raise ValueError("MVGAE needs image and text features (its forward reads both encoders)")
@@ -203,6 +210,10 @@ class MVGAE(FusedEvalMixin, GeneralRecommender):
         hardest = torch.mm(zu, z[neg_items].t()).max(dim=-1).values          # == max_j <z[user_b], z[neg_j]>
         return -torch.sum(torch.log2(torch.sigmoid(pos - torch.sigmoid(hardest))))
 
+    def _fused_recon_loss(self, z, user, pos_items, neg_items):
+        """recon_loss with the `fused_recon` key on: one latent of the op"""
+        return hip_ops.hardest_negative_loss(z.unsqueeze(0), user, pos_items, neg_items)[0]
+
     def kl_loss(self, mu, logvar):
         logvar = logvar.clamp(max=MAX_LOGVAR)
         return -0.5 * torch.mean(torch.sum(1 + logvar - mu ** 2 - logvar.exp(), dim=1))
@@ -215,6 +226,8 @@ class MVGAE(FusedEvalMixin, GeneralRecommender):
         ops = [t.contiguous() for t in (v_mu, v_logvar, t_mu, t_logvar, c_mu, c_logvar)]
         noise = [torch.randn_like(ops[1]) for _ in range(4)] if self.training else None     # the composition's order: pd, v, t, c
         z, kl, self.result_embed = hip_ops.posterior_fusion(*ops, noise)
+        if self.fused_recon:                                          # the four reconstruction terms: one call, no [4, 3 B, 64] rows
+            return hip_ops.hardest_negative_loss(z, user, pos_items, neg_items).sum() + self.beta * kl.sum()
         b = user.shape[0]
         rows = torch.sigmoid(z.index_select(1, torch.cat((user, pos_items, neg_items))))    # [4, 3 B, 64]
         zu, zp, zn = rows[:, :b], rows[:, b:2 * b], rows[:, 2 * b:]
@@ -231,7 +244,8 @@ class MVGAE(FusedEvalMixin, GeneralRecommender):
         z_v = self.reparametrize(v_mu, v_logvar)
         z_t = self.reparametrize(t_mu, t_logvar)
         z_c = self.reparametrize(c_mu, c_logvar)
-        loss = self.recon_loss(z, user, pos_items, neg_items) + self.beta * self.kl_loss(pd_mu, pd_logvar)
+        recon_loss = self._fused_recon_loss if self.fused_recon else self.recon_loss
+        loss = recon_loss(z, user, pos_items, neg_items) + self.beta * self.kl_loss(pd_mu, pd_logvar)
         for zz, mu, lv in ((z_v, v_mu, v_logvar), (z_t, t_mu, t_logvar), (z_c, c_mu, c_logvar)):
-            loss = loss + self.recon_loss(zz, user, pos_items, neg_items) + self.beta * self.kl_loss(mu, lv)
+            loss = loss + recon_loss(zz, user, pos_items, neg_items) + self.beta * self.kl_loss(mu, lv)
         return loss

@@ -683,6 +683,8 @@ class _LightGCNMeanParts(torch.autograd.Function):
 
 def lightgcn_mean_parts(g: CsrGraph, parts, n_layers):
     """mean_l(A^l cat(parts)) as a tuple of row blocks, one per input table (freedom.py:165-178: cat, propagate, split)"""
+    if isinstance(g, PermutedGraph):      # the node launches on a CsrGraph: a relabelled graph goes through lightgcn_mean
+        return tuple(lightgcn_mean(g, torch.cat(list(parts), dim=0), n_layers).split([p.shape[0] for p in parts]))
     return _LightGCNMeanParts.apply(g, n_layers, *parts)
 
 

@@ -520,7 +520,8 @@ def test_propagation_read_at_batch_rows_equals_the_dense_autograd(ops, dev, d, L
     rows and the item-item layer pulled at listed rows == the dense ops read at those rows BIT FOR BIT in the forward; the
     backward (compact gradient -> push through the listed rows, then L - 1 full launches) == the dense autograd to rounding.
     A user-item graph with hub rows of thousands of nonzeros (one workgroup per pushed row), duplicated batch rows, a directed
-    20-nonzero item-item graph."""
+    20-nonzero item-item graph.  (HIP against HIP; the same nodes against float64, on directed graphs and every fallback:
+    tests/test_batch_rows_fuzz_gpu.py.)"""
     rng = np.random.default_rng(10 * d + L)
     nu, ni = 900, 400
     from mmrec_amd import synth

@@ -11,9 +11,14 @@ Step counts.  `capturable=False`: every parameter follows its OWN count, as torc
 `.grad` in some step is skipped and its bias corrections lag the others'.  `capturable=True`: a parameter group has ONE device
 counter, advanced once per `step()`, and every parameter updated in that step takes the GROUP's bias corrections, also one
 that was skipped earlier (torch's capturable Adam keeps a counter per parameter).  This is intended: a captured step cannot
-branch on which gradients exist, and every parameter of the models here receives a gradient in every step; the host mirror
+branch on which gradients exist, and every parameter of a replayed step receives a gradient in every replay; the host mirror
 `state[p]['step']` counts the parameter's own updates only until `state_dict()` is called, which overwrites every
-parameter's `step` with the group's device count (the count a resumed run continues from).  tests/test_adam_fuzz_gpu.py pins both behaviours."""
+parameter's `step` with the group's device count (the count a resumed run continues from).  tests/test_adam_fuzz_gpu.py pins both behaviours.
+The exception: a parameter WITHOUT a gradient when a step is captured is no part of the replayed step, so only eager steps ever
+update it (LATTICE's graph learner: the eager first batch of every epoch) and its host mirror is exact.  Such a parameter keeps its
+OWN count, as under `capturable=False` and in torch.optim.Adam, in the eager steps and in `state_dict()`: with the group's count
+its second update took the bias corrections of step 8 instead of 2, and LATTICE replayed ended 1.8e-4 away from LATTICE eager
+after two epochs (tests/test_graph_step_models_gpu.py)."""
 import ctypes
 
 import torch
@@ -32,6 +37,7 @@ class HipAdam(torch.optim.Optimizer):
         self.capturable = capturable
         self.multi_tensor = multi_tensor   # one launch per parameter group (<= 24 tensors each) instead of one per tensor
         self._dev = {}   # id(group) -> (step int64[1], lr fp32[1], hyper fp32[2]) when capturable
+        self._own_count = set()   # id(p) of parameters the last captured step left out (no gradient): they keep their own count
         # config `reorder` (models/_base.py: RelabelledIdsMixin): the per-row state of a relabelled table -- both moments -- lives in
         # the table's row order.  The Trainer registers the tables' permutations here, and a checkpoint then holds that state in the
         # DATASET's row order like the model's state_dict does (it loads under any `reorder`, or none); the tag is saved with it
@@ -98,7 +104,7 @@ class HipAdam(torch.optim.Optimizer):
                 if id(group) in self._dev:
                     n = int(self._dev[id(group)][0].item())
                     for p in group['params']:
-                        if p in self.state and self.state[p]:
+                        if p in self.state and self.state[p] and id(p) not in self._own_count:
                             self.state[p]['step'] = n
         sd = super().state_dict()
         if self._row_orders:
@@ -160,12 +166,13 @@ class HipAdam(torch.optim.Optimizer):
                 loss = closure()
         lib = _lib.load()
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        capturing = self.capturable and torch.cuda.is_current_stream_capturing()
         for group in self.param_groups:
             b1, b2 = group['betas']
             hyper = None
             if self.capturable:
                 step_dev, lr_dev, hyper = self._group_dev(group)
-                if not torch.cuda.is_current_stream_capturing():
+                if not capturing:
                     lr_dev.fill_(float(group['lr']))
                 _lib.check(lib.mmrec_adam_prepare(_ptr(step_dev), _ptr(lr_dev), float(b1), float(b2),
                                                   _ptr(hyper), stream), "adam_prepare")
@@ -182,42 +189,56 @@ class HipAdam(torch.optim.Optimizer):
                         st['step'] += 1
                     continue
                 if p.grad is None:
+                    if capturing and p.requires_grad:     # no part of the replayed step: only eager steps update it
+                        self._own_count.add(id(p))
                     continue
+                if capturing:
+                    self._own_count.discard(id(p))
                 if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                     raise _lib.MMRecHipError("HipAdam needs contiguous fp32 device parameters")
                 st = self._moments(p)
                 st['step'] += 1   # host mirror (exact outside graph replays)
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 todo.append((p, g, st))
-            if not todo:
-                continue
-            if not self.multi_tensor:
-                for p, g, st in todo:
-                    if self.capturable:
-                        _lib.check(lib.mmrec_adam_step_dev_f32(
-                            _ptr(p), _ptr(g), _ptr(st['exp_avg']), _ptr(st['exp_avg_sq']), p.numel(), _ptr(hyper),
-                            float(b1), float(b2), float(group['eps']), float(group['weight_decay']), stream),
-                            "adam_step_dev")
-                    else:
-                        _lib.check(lib.mmrec_adam_step_f32(
-                            _ptr(p), _ptr(g), _ptr(st['exp_avg']), _ptr(st['exp_avg_sq']), p.numel(),
-                            float(group['lr']), float(b1), float(b2), float(group['eps']),
-                            float(group['weight_decay']), int(st['step']), stream), "adam_step")
-                continue
-            # one launch for the whole group: host arrays of device pointers, copied into the kernel arguments
-            k = len(todo)
-            ptrs = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
-            pp, gg = ptrs([t[0] for t in todo]), ptrs([t[1] for t in todo])
-            mm, vv = ptrs([t[2]['exp_avg'] for t in todo]), ptrs([t[2]['exp_avg_sq'] for t in todo])
-            nn_ = (ctypes.c_int64 * k)(*[t[0].numel() for t in todo])
-            if self.capturable:
-                _lib.check(lib.mmrec_adam_multi_step_dev_f32(
-                    pp, gg, mm, vv, nn_, k, _ptr(hyper), float(b1), float(b2), float(group['eps']),
-                    float(group['weight_decay']), stream), "adam_multi_step_dev")
-            else:
-                lrs = (ctypes.c_float * k)(*[float(group['lr'])] * k)
-                steps = (ctypes.c_int64 * k)(*[int(t[2]['step']) for t in todo])
-                _lib.check(lib.mmrec_adam_multi_step_f32(
-                    pp, gg, mm, vv, nn_, k, lrs, steps, float(b1), float(b2), float(group['eps']),
-                    float(group['weight_decay']), stream), "adam_multi_step")
+            if self.capturable and not capturing and self._own_count:
+                # parameters the captured step left out take their own count's bias corrections (exact on the host)
+                self._launch(lib, stream, group, [t for t in todo if id(t[0]) in self._own_count], None)
+                todo = [t for t in todo if id(t[0]) not in self._own_count]
+            self._launch(lib, stream, group, todo, hyper)
         return loss
+
+    def _launch(self, lib, stream, group, todo, hyper):
+        """the update of `todo` [(p, grad, state)]: bias corrections from the device scalars `hyper` (capturable), or with
+        hyper None from the host learning rate and every parameter's own host count"""
+        if not todo:
+            return
+        b1, b2 = group['betas']
+        if not self.multi_tensor:
+            for p, g, st in todo:
+                if hyper is not None:
+                    _lib.check(lib.mmrec_adam_step_dev_f32(
+                        _ptr(p), _ptr(g), _ptr(st['exp_avg']), _ptr(st['exp_avg_sq']), p.numel(), _ptr(hyper),
+                        float(b1), float(b2), float(group['eps']), float(group['weight_decay']), stream),
+                        "adam_step_dev")
+                else:
+                    _lib.check(lib.mmrec_adam_step_f32(
+                        _ptr(p), _ptr(g), _ptr(st['exp_avg']), _ptr(st['exp_avg_sq']), p.numel(),
+                        float(group['lr']), float(b1), float(b2), float(group['eps']),
+                        float(group['weight_decay']), int(st['step']), stream), "adam_step")
+            return
+        # one launch for the whole group: host arrays of device pointers, copied into the kernel arguments
+        k = len(todo)
+        ptrs = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
+        pp, gg = ptrs([t[0] for t in todo]), ptrs([t[1] for t in todo])
+        mm, vv = ptrs([t[2]['exp_avg'] for t in todo]), ptrs([t[2]['exp_avg_sq'] for t in todo])
+        nn_ = (ctypes.c_int64 * k)(*[t[0].numel() for t in todo])
+        if hyper is not None:
+            _lib.check(lib.mmrec_adam_multi_step_dev_f32(
+                pp, gg, mm, vv, nn_, k, _ptr(hyper), float(b1), float(b2), float(group['eps']),
+                float(group['weight_decay']), stream), "adam_multi_step_dev")
+        else:
+            lrs = (ctypes.c_float * k)(*[float(group['lr'])] * k)
+            steps = (ctypes.c_int64 * k)(*[int(t[2]['step']) for t in todo])
+            _lib.check(lib.mmrec_adam_multi_step_f32(
+                pp, gg, mm, vv, nn_, k, lrs, steps, float(b1), float(b2), float(group['eps']),
+                float(group['weight_decay']), stream), "adam_multi_step")

@@ -21,6 +21,8 @@ from mmrec_amd.models._base import FusedEvalMixin, GeneralRecommender
 
 
 class SELFCFED_LGN(FusedEvalMixin, GeneralRecommender):
+    graph_capturable = False      # the encoder's edge-dropout rate is a host-side numpy draw per batch: a capture would freeze it
+
     def __init__(self, config, dataset):
         super().__init__(config, dataset)
         self.user_count, self.item_count = self.n_users, self.n_items

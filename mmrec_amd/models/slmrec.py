@@ -162,9 +162,10 @@ class SLMRec(FusedEvalMixin, GeneralRecommender):
         return F.cross_entropy(logits, torch.arange(a.shape[0], device=a.device))
 
     def infonce(self, users, pos):
-        self.all_users, self.all_items = self.compute()
+        all_users, all_items = self.compute()
+        self.all_users, self.all_items = all_users.detach(), all_items.detach()     # what the evaluation reuses: values only
         ids = torch.arange(users.shape[0], device=users.device)
-        return hip_ops.infonce(self.all_users[users].contiguous(), self.all_items[pos].contiguous(), ids, self.temp)
+        return hip_ops.infonce(all_users[users].contiguous(), all_items[pos].contiguous(), ids, self.temp)
 
     def fac(self, idx):
         x_i_iv = _lin(self.g_i_iv, self.i_emb_i[idx])
@@ -177,4 +178,8 @@ class SLMRec(FusedEvalMixin, GeneralRecommender):
     def calculate_loss(self, interaction):
         users, pos = interaction[0], interaction[1]
         main_loss = self.infonce(users, pos)
-        return main_loss + self.config['ssl_alpha'] * self.fac(pos)
+        loss = main_loss + self.config['ssl_alpha'] * self.fac(pos)
+        # nothing on `self` keeps this step's autograd graph alive after it: a later step captured as a hipGraph would meet the
+        # gradient accumulators of this one, bound to another stream (the capture then ended in a segmentation fault)
+        self.i_emb_u = self.i_emb_i = self.v_emb_u = self.v_emb_i = self.t_emb_u = self.t_emb_i = None
+        return loss

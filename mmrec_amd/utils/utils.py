@@ -83,8 +83,11 @@ def random_sample_range(n, k):
 
 def graph_step_mode(config):
     """`hip_graph_step`: True / False, or absent / 'auto' = replay the training step as a hipGraph for the plugins that
-    declare `graph_capturable = True` (verified: same kernels in the same order, tests/test_models_gpu.py) and run every
-    other model -- anything a user drops in -- eagerly."""
+    declare `graph_capturable = True` (LayerGCN, LightGCN, BPR, VBPR, FREEDOM, BM3, MMGCN, LATTICE) and run every other model
+    -- anything a user drops in -- eagerly.  True also replays the plugins without the flag (GRCN, DualGNN, DRAGON, MGCN, SMORE,
+    PGL, SLMRec, MMGCF); a plugin with `graph_capturable = False` (LGMRec, MVGAE, DAMRS, SELFCFED_LGN: each says why) never
+    replays.  Verified for every plugin of the first two lists -- two replayed epochs against two eager ones: losses, parameters
+    and Adam moments -- by tests/test_graph_step_models_gpu.py, which also keeps the three lists complete."""
     v = config['hip_graph_step']
     if v is None or str(v).lower() == 'auto':
         return 'auto'

@@ -1056,6 +1056,44 @@ int mmrec_hardest_neg_bwd_f32(const float* Z, int64_t N, int32_t L, int32_t d, c
                               const int64_t* neg, int32_t B, int32_t squash, const int32_t* arg, const float* coef,
                               const float* su, const float* g, float* G, mmrec_stream_t stream);
 
+/* DAMRS's symmetric KL term between two views of the user-item probabilities, never storing an [m, n] block; with its backward.
+ * ADDITIVE to ABI 16: four new symbols, nothing existing changes, MMREC_ABI_VERSION stays 16.
+ * replaces: p_g = sigmoid(n_u @ normalize(item_emb[i_id]).T), p_m = sigmoid(n_u @ normalize(it_emb[i_id]).T),
+ *           mean(_kl(p_g, p_m) + _kl(p_m, p_g)) -- damrs.py, two GEMMs and about thirty elementwise launches over [m, n] blocks --
+ *           and autograd's mirror of it.
+ * U [m, 64], A [n, 64], B [n, 64] fp32 row-major.  With a = <U[r], A[i]>, b = <U[r], B[i]>, p = sigmoid(a), q = sigmoid(b) (the
+ * sigmoid of mmrec_hardest_neg_fwd_f32: e = expf(-|z|), (z >= 0 ? 1 : e) / (1 + e)) the two divergences collapse:
+ *   KL(p || q) + KL(q || p) = (p - q)(logit p - logit q) = (p - q)(a - b) =: J(a, b)
+ *   out[0] = scale * sum_{r < m, i < n} J(a_ri, b_ri)                         (the caller's scale: 1 / (m n) for the mean)
+ *   ga_ri  = g scale [p (1 - p)(a - b) + (p - q)],   gb_ri = -g scale [q (1 - q)(a - b) + (p - q)]      g [1] ON THE DEVICE
+ *   dU = Ga A + Gb B,   dA = Ga^T U,   dB = Gb^T U                            any of dU, dA, dB may be NULL (not computed)
+ * J is finite for every finite a and b; the composition it replaces is NaN (0 * log 0) once a sigmoid saturates in fp32.
+ * THE PLAN.  Scores are the fp32 fma chains of the fp32-input MFMA in natural k order, the same bits in all three sweeps.
+ *   forward  grid (ceil(m / 128) tiles of U) x (splits of the items); a split walks mmrec_mutual_kl_split_cols(m, n, 0) rows of
+ *            A and B, staged together.  A lane adds the J of its pairs in the order it meets them (16 per 32-row sub-tile), the 64
+ *            lanes of a wave by a butterfly (xor 32, 16, 8, 4, 2, 1), the four waves in order: one partial per workgroup.  The
+ *            finish is ONE workgroup of 256 threads: thread t adds the partials t, t + 256, ... in order, then the same butterfly
+ *            and the four waves in order, then the product with scale.
+ *   backward recomputes a, b, p, q.  The dU sweep owns 128 rows of U and walks mmrec_mutual_kl_split_cols(m, n, 1) rows of A and B
+ *            per split (per 32-row sub-tile: Ga A, then Gb B, into one accumulator); ONE sweep owns 128 item rows of A and B
+ *            together and walks mmrec_mutual_kl_split_cols(m, n, 2) rows of U per split for dA and dB.  Products on the MFMA in
+ *            the walked side's order; per-split partial gradients are added in split order.  A sweep none of whose gradients
+ *            is wanted is not launched.
+ * Rows past the end of a tile are zero rows: J(0, 0) = 0 and both coefficients are exactly 0, no mask anywhere.  NO ATOMICS, every
+ * order fixed by (m, n) alone: two calls on the same inputs give the same bits, forward and gradients.
+ * m == 0 or n == 0: out = 0 and zero gradients.  Outputs must not alias inputs.
+ * workspace: mmrec_mutual_kl_workspace_bytes(m, n, d) bytes (16-byte aligned) serve either call: one float per forward workgroup;
+ * for the backward the per-split partial gradients, at most 4 (m + n) 64 floats for each of dU, dA, dB.  0 for d != 64 or no pair.
+ * d != 64 or a negative size: MMREC_ERR_BAD_ARG; m or n > 2^30: MMREC_ERR_UNSUPPORTED; a NULL out, a NULL U / A / B / g /
+ * workspace where it is needed, dU, dA and dB all NULL: MMREC_ERR_BAD_ARG -- before any launch.  No synchronisation, no
+ * allocation, no data-dependent launch shape, capture-safe, no global state. */
+int32_t mmrec_mutual_kl_split_cols(int32_t m, int32_t n, int32_t mode);
+size_t mmrec_mutual_kl_workspace_bytes(int32_t m, int32_t n, int32_t d);
+int mmrec_mutual_kl_f32(const float* U, const float* A, const float* B, int32_t m, int32_t n, int32_t d, float scale, float* out,
+                        void* workspace, mmrec_stream_t stream);
+int mmrec_mutual_kl_bwd_f32(const float* U, const float* A, const float* B, int32_t m, int32_t n, int32_t d, float scale,
+                            const float* g, float* dU, float* dA, float* dB, void* workspace, mmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P5 / P6  fused scoring + mask + top-K:  for every query row q: top-k over c of <Q[q], C[c]>,
  *          skipping candidates listed for q in a CSR mask (train positives), never materialising

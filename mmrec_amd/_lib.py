@@ -123,6 +123,10 @@ SIGNATURES = {
     "mmrec_hardest_neg_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "mmrec_hardest_neg_fwd_f32": (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "mmrec_hardest_neg_bwd_f32": (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    "mmrec_mutual_kl_split_cols": (c_int32, [c_int32, c_int32, c_int32]),
+    "mmrec_mutual_kl_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "mmrec_mutual_kl_f32": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P]),
+    "mmrec_mutual_kl_bwd_f32": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P]),
     "mmrec_gemm_nt_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     "mmrec_topk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "mmrec_score_topk_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P,

@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libmmrec_hip.so")
-SOURCES = ["api.hip", "spmm.hip", "spmm_narrow.hip", "bpr.hip", "infonce.hip", "gemm.hip", "topk.hip", "topk_filter.hip", "graph.hip", "evalsample.hip", "adam.hip", "layer_ew.hip", "edge.hip", "edge_softmax.hip", "edge_attention.hip", "score_lse.hip", "neighbor_max.hip", "hypergraph.hip", "hypergraph64.hip", "spectrum.hip", "tri_topk.hip", "modal_fusion.hip", "posterior.hip", "encoder_heads.hip", "gcn_layer.hip", "hardest_neg.hip"]
+SOURCES = ["api.hip", "spmm.hip", "spmm_narrow.hip", "bpr.hip", "infonce.hip", "gemm.hip", "topk.hip", "topk_filter.hip", "graph.hip", "evalsample.hip", "adam.hip", "layer_ew.hip", "edge.hip", "edge_softmax.hip", "edge_attention.hip", "score_lse.hip", "neighbor_max.hip", "hypergraph.hip", "hypergraph64.hip", "spectrum.hip", "tri_topk.hip", "modal_fusion.hip", "posterior.hip", "encoder_heads.hip", "gcn_layer.hip", "hardest_neg.hip", "mutual_kl.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wno-unused-result"]
 EXTRA_FLAGS = {}    # per-file extras: {source name: [flags]}

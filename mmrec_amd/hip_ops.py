@@ -3437,6 +3437,80 @@ def hardest_negative_loss(Z, users, pos, neg, squash=True, return_arg=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# DAMRS's symmetric KL term (csrc/mutual_kl.hip): mean over users x items of KL(p || q) + KL(q || p), no [users, items] block
+# ------------------------------------------------------------------------------------------------
+def mutual_kl_split_cols(m, n, mode=0):
+    """rows of A and B one workgroup of the forward walks (the library's plan for the shape); mode 1: the same for the dU
+    sweep, mode 2: the rows of U one workgroup of the dA / dB sweep walks"""
+    return int(_lib.load().mmrec_mutual_kl_split_cols(int(m), int(n), int(mode)))
+
+
+def _bernoulli_kl(p1, p2):
+    """DAMRS._kl (models/damrs.py), term for term"""
+    return p1 * torch.log(p1) - p1 * torch.log(p2) + (1 - p1) * torch.log(1 - p1) - (1 - p1) * torch.log(1 - p2)
+
+
+def mutual_kl_torch(U, A, B):
+    """exactly DAMRS's composition: p_g = sigmoid(U @ A.T), p_m = sigmoid(U @ B.T), mean(_kl(p_g, p_m) + _kl(p_m, p_g)); stock
+    autograd, about twenty [m, n] blocks kept.  NaN (0 * log 0) once a logit saturates fp32's sigmoid, |logit| >~ 17."""
+    p_g = torch.sigmoid(torch.mm(U, A.t()))
+    p_m = torch.sigmoid(torch.mm(U, B.t()))
+    return torch.mean(_bernoulli_kl(p_g, p_m) + _bernoulli_kl(p_m, p_g))
+
+
+def mutual_kl_served(U, A, B):
+    """True where `mutual_kl` runs the kernels: device fp32 contiguous U [m, 64], A [n, 64], B [n, 64] with m, n >= 1"""
+    return bool(_fuser_table(U) and _fuser_table(A) and _fuser_table(B) and A.shape[0] == B.shape[0])
+
+
+class _MutualKL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, A, B):
+        lib = _lib.load()
+        m, n = U.shape[0], A.shape[0]
+        scale = 1.0 / (float(m) * float(n))                  # in double on the host, rounded once to fp32 by the call
+        out = torch.empty((), dtype=torch.float32, device=U.device)
+        ws = _ws(lib.mmrec_mutual_kl_workspace_bytes(m, n, EMB_DIM), U.device)
+        _lib.check(lib.mmrec_mutual_kl_f32(_p(U), _p(A), _p(B), m, n, EMB_DIM, scale, _p(out), _p(ws), _stream()), "mutual_kl")
+        ctx.scale = scale
+        ctx.save_for_backward(U, A, B)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        want = ctx.needs_input_grad[:3]
+        if not any(want):
+            return None, None, None
+        lib = _lib.load()
+        U, A, B = ctx.saved_tensors
+        m, n = U.shape[0], A.shape[0]
+        g = g.contiguous()
+        dU, dA, dB = (torch.empty_like(t) if w else None for t, w in zip((U, A, B), want))
+        ws = _ws(lib.mmrec_mutual_kl_workspace_bytes(m, n, EMB_DIM), U.device)
+        _lib.check(lib.mmrec_mutual_kl_bwd_f32(_p(U), _p(A), _p(B), m, n, EMB_DIM, ctx.scale, _p(g), _p(dU), _p(dA), _p(dB),
+                                               _p(ws), _stream()), "mutual_kl_bwd")
+        return dU, dA, dB
+
+
+def mutual_kl(U, A, B):
+    """DAMRS's KL term -> the scalar mean over r < m, i < n of KL(p || q) + KL(q || p) of the Bernoulli pairs
+    p = sigmoid(<U[r], A[i]>), q = sigmoid(<U[r], B[i]>), with autograd to all three operands, never holding an [m, n] block.
+    The two divergences collapse: with a, b the two logits, KL(p || q) + KL(q || p) = (p - q)(a - b) =: J(a, b) -- no
+    logarithm.  Served by the kernels (`mutual_kl_served`: device fp32 contiguous [m, 64], [n, 64], [n, 64], m, n >= 1): one
+    fp32-MFMA sweep of 128 rows of U against 64-row tiles of A and B staged together plus a fixed-order finish; the backward
+    recomputes the logits, one sweep for dU = Ga A + Gb B and one, owning the rows of A and B together, for dA = Ga^T U and
+    dB = Gb^T U, a sweep whose gradients nobody wants skipped.  The scale 1 / (m n) is computed on the host in double.  No
+    atomics: the same bits every call, so `DETERMINISTIC` changes nothing; the plan depends on (m, n) alone: capturable.
+    SATURATION: the composition below returns NaN once a logit saturates fp32's sigmoid (|logit| >~ 17: 0 * log 0); J, and
+    so the kernels, stay finite for any finite logits.  Below that the two agree within fp32 rounding.
+    EVERY OTHER CASE (CPU tensors, a width other than 64, other dtypes, non-contiguous or empty operands) is exactly
+    `mutual_kl_torch`, the model's composition with stock autograd."""
+    if mutual_kl_served(U, A, B):
+        return _MutualKL.apply(U, A, B)
+    return mutual_kl_torch(U, A, B)
+
+
+# ------------------------------------------------------------------------------------------------
 # MVGAE's encoder heads (csrc/encoder_heads.hip): H normalised convolutions of one aggregated table, output and skip Linears
 # ------------------------------------------------------------------------------------------------
 ENCODER_HEADS = True   # False: every encoder_heads call is `encoder_heads_torch` (A/B runs)

@@ -10,7 +10,11 @@ discrimination term are read out of the similarity block instead of being re-com
 tensor.  With the config key `fused_labels: True` (absent / False: that path, untouched) the neighbour term holds no
 [b, I] block: the labels come from `hip_ops.pseudo_labels` (csrc/tri_topk.hip: one sweep over the three tables for the
 three mixed top-10 lists, the second lists out of the top-20 cosines), the row totals from `hip_ops.score_lse` and the
-twenty positive cosines per row from `hip_ops.edge_dot`; the KL term's [users, items] blocks stay.
+twenty positive cosines per row from `hip_ops.edge_dot`; the KL term's [users, items] blocks stay.  With `fused_kl: True`
+(absent / False: the composition, untouched) they go too: the KL term is `hip_ops.mutual_kl` (csrc/mutual_kl.hip: the two
+divergences collapse to (p_g - p_m)(logit p_g - logit p_m), swept on the fp32 MFMA, forward and backward) on the gathered user
+rows and the two row-normalised item gathers; with both keys on the loss holds no two-dimensional block.  The composition is
+NaN once a logit saturates fp32's sigmoid; the collapsed form stays finite.
 
 Reference behaviour kept: image_trs / text_trs exist (and are saved) but take no part in anything; the weights stored
 in the item-graph file are ignored (a 0/1 adjacency is normalised); items missing from the file keep only their self
@@ -101,6 +105,7 @@ class DAMRS(FusedEvalMixin, GeneralRecommender):
                 s_cols.append(nb)
         self.session_adj = sym_normalised_graph(np.concatenate(s_rows), np.concatenate(s_cols), self.n_items, self.device)
         self.fused_labels = bool(config['fused_labels']) if 'fused_labels' in config else False    # new key, default off
+        self.fused_kl = bool(config['fused_kl']) if 'fused_kl' in config else False                # new key, default off
 
     # ---- propagation
     def _item_graph(self, graph):
@@ -140,6 +145,15 @@ class DAMRS(FusedEvalMixin, GeneralRecommender):
     def _kl(p1, p2):
         return p1 * torch.log(p1) - p1 * torch.log(p2) + (1 - p1) * torch.log(1 - p1) - (1 - p1) * torch.log(1 - p2)
 
+    def _kl_term(self, n_u, items_g, items_m):
+        """the symmetric KL between the user-item probabilities of the graph view and of the modal view; `fused_kl`: no
+        [users, items] block (hip_ops.mutual_kl on the row-normalised gathers)"""
+        if self.fused_kl:
+            return hip_ops.mutual_kl(n_u, hip_ops.row_normalize(items_g), hip_ops.row_normalize(items_m))
+        p_g = torch.sigmoid(torch.mm(n_u, F.normalize(items_g, dim=-1).t()))
+        p_m = torch.sigmoid(torch.mm(n_u, F.normalize(items_m, dim=-1).t()))
+        return torch.mean(self._kl(p_g, p_m) + self._kl(p_m, p_g))
+
     @staticmethod
     def _modal_weights(u, h_t, h_v, h_s, pos_items, neg_items):
         with torch.no_grad():
@@ -175,9 +189,7 @@ class DAMRS(FusedEvalMixin, GeneralRecommender):
         neighbour = self._neighbour_fused(i_id, (h_t, h_v, h_s))
         n_u = user_emb[u_id]
         it_emb = (h_t + h_s + h_v) / 3.0
-        p_g = torch.sigmoid(torch.mm(n_u, F.normalize(item_emb[i_id], dim=-1).t()))
-        p_m = torch.sigmoid(torch.mm(n_u, F.normalize(it_emb[i_id], dim=-1).t()))
-        kl = torch.mean(self._kl(p_g, p_m) + self._kl(p_m, p_g))
+        kl = self._kl_term(n_u, item_emb[i_id], it_emb[i_id])
         u = user_emb[users]
         pos_w, neg_w = self._modal_weights(u, h_t, h_v, h_s, pos_items, neg_items)
         ia = item_emb + (h_t + h_v + h_s) / 3.0
@@ -202,9 +214,7 @@ class DAMRS(FusedEvalMixin, GeneralRecommender):
                      + self._neighbour_discrimination(*labels_t, cos_t)) / 3.0
         n_u = user_emb[u_id]
         it_emb = (h_t + h_s + h_v) / 3.0
-        p_g = torch.sigmoid(torch.mm(n_u, F.normalize(item_emb[i_id], dim=-1).t()))
-        p_m = torch.sigmoid(torch.mm(n_u, F.normalize(it_emb[i_id], dim=-1).t()))
-        kl = torch.mean(self._kl(p_g, p_m) + self._kl(p_m, p_g))
+        kl = self._kl_term(n_u, item_emb[i_id], it_emb[i_id])
         u = user_emb[users]
         pos_w, neg_w = self._modal_weights(u, h_t, h_v, h_s, pos_items, neg_items)
         ia = item_emb + (h_t + h_v + h_s) / 3.0
